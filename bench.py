@@ -1,6 +1,15 @@
 """Benchmark: BPR triplets/sec on the ml-20m-shaped workload (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W [--batch-size B]
+  python bench.py --gpus N --steps K --warmup W [--batch-size B] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes its outputs if --dump-outputs is given and
+prints the result line (value, ms_per_step).  --full adds the legs that take runs of their own: the
+per-kernel event pass behind `roofline`, the relaxed_local / relaxed_local_hbm sub-objects and
+cpu_baseline (each still switched off by its --no-... option).
+--dump-outputs DIR: after the timed steps, the tables a caller of the timed path would read back
+(get_weights(): P, Q) and the last call's loss, as DIR/<name>.npy in float32 / float64; tables of
+more than 64 MB in all are written as a fixed, seeded sample of their rows.  Positives, init and
+sampling are functions of --seed, so two builds run with the same arguments see the same inputs.
 
 A "step" = one BPR-MF training step over one batch of B triplets per GPU: on-device negative
 sampling + batch build (amortised: one build launch per chunk of steps, inside the timed region),
@@ -13,13 +22,13 @@ positives (lognormal degree, Zipf items), d=128, num_ng=4, lr=0.01, wd=0.001, B=
 reference CLI defaults, BPRMFRecommender.py:53-116).
 
 Prints ONE JSON line (rank 0).
-roofline: algorithmic bytes per step = B*(24d+12) (3 rows read + 3 rows written + 3 int32 ids per
-  triplet) over the live HIP-event time of the step's two kernels (user_step +
+roofline (--full): algorithmic bytes per step = B*(24d+12) (3 rows read + 3 rows written + 3 int32
+  ids per triplet) over the live HIP-event time of the step's two kernels (user_step +
   item_step, which together do that gather/scatter), peak 8 TB/s HBM3E.  The event pass runs right
   after the timed region over the same number of steps (per-launch events perturb the timing, so
   they are kept out of the timed region); rocprofv3 summaries of the same command: profiles/.
-cpu_baseline: the oracle's C port of the reference step (dense grads + dense weight decay, as torch
-  does) and of the sampler, timed on this host on a bounded sample; the reference's own torch-CPU
+cpu_baseline (--full): the oracle's C port of the reference step (dense grads + dense weight decay,
+  as torch does) and of the sampler, timed on this host on a bounded sample; the reference's own torch-CPU
   step (measured in the build container) is quoted beside it.
 --semantics hogwild: the opt-in relaxed mode (csrc/hogwild.hip; not the reference step) on the
   same workload, labelled as such in config.semantics; the default line is the exact step.
@@ -184,8 +193,32 @@ def relaxed_local_hbm(rl, syn, d, B, seed, local_steps, steps, warmup):
     return r
 
 
+DUMP_BUDGET_BYTES = 60_000_000  # --dump-outputs: under 64 MB in all
+
+
+def dump_outputs(path, arrays, suffix=""):
+    """Write {name: array} as path/<name><suffix>.npy (float32 stays, everything else float64).
+    More than DUMP_BUDGET_BYTES in all: the same seeded sample of rows of every array, run to run."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float32 if np.asarray(v).dtype == np.float32 else np.float64)
+              for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    g = np.random.default_rng(0)
+    for k, v in arrays.items():
+        if total > DUMP_BUDGET_BYTES and v.ndim >= 1 and len(v) > 1:
+            keep = max(1, int(len(v) * DUMP_BUDGET_BYTES / total))
+            v = v[np.sort(g.choice(len(v), keep, replace=False))]
+        np.save(os.path.join(path, f"{k}{suffix}.npy"), v)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline: the per-kernel event pass (roofline), "
+                         "relaxed_local, relaxed_local_hbm and cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the tables (P, Q) and the last call's loss as "
+                         "DIR/<name>.npy")
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=4000)
     ap.add_argument("--warmup", type=int, default=400)
@@ -227,6 +260,10 @@ def main():
                     help="process group backend (gloo: rehearse several ranks on one GPU, IPC "
                          "transport; RCCL refuses two ranks on one device)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not a.full:  # a plain run: the headline's timed steps only
+        a.no_profile = a.no_relaxed = a.no_cpu_baseline = True
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -270,12 +307,13 @@ def main():
         n_steps = m.epoch_size()[1]
 
         def run(first, k):
-            done = 0
+            done, st = 0, None
             while done < k:
                 e, s = divmod(first + done, n_steps)
                 c = min(k - done, n_steps - s)
-                m.train_steps(e, s, c)
+                st = m.train_steps(e, s, c)
                 done += c
+            return st
     else:
         m = rl.ShardedBPRMF(U, I, d, lr=0.01, wd=0.001, batch_size=B, num_ng=4, seed=a.seed,
                             device=local, semantics=a.semantics, local_steps=a.local_steps,
@@ -290,12 +328,13 @@ def main():
             m.attach_runner(a.transport)
 
             def run(first, k):
-                done = 0
+                done, st = 0, None
                 while done < k:
                     e, s = divmod(first + done, n_steps)
                     c = min(k - done, n_steps - s)
-                    m.train_steps(e, s, c)
+                    st = m.train_steps(e, s, c)
                     done += c
+                return st
 
     # the timing barriers: the ranks of one node meet on shared memory (bprmf_node_barrier_*,
     # ~1 us); a process group's barrier (gloo sockets, or the nccl group's device all-reduce plus a
@@ -320,11 +359,13 @@ def main():
         elif dist and world > 1:  # (one rank: nothing to wait for)
             dist.barrier(group=bar)
 
+    last = {}  # the last call's return value (train_steps: its stats)
+
     def timed(first, k):
         barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        run(first, k)
+        last["stats"] = run(first, k)
         torch.cuda.synchronize()
         barrier()
         el = time.perf_counter() - t0
@@ -339,6 +380,13 @@ def main():
     xs0 = m.exchange_stats() if sharded and not a.python_orchestration else None
     el = timed(a.warmup, a.steps)
     xs1 = m.exchange_stats() if xs0 is not None else None
+    if a.dump_outputs:  # what the timed steps left, before any further pass trains on
+        P, Q = m.get_weights()
+        arrays = {"P": P, "Q": Q}
+        if isinstance(last.get("stats"), dict) and "loss" in last["stats"]:
+            arrays["loss"] = np.array([last["stats"]["loss"]], dtype=np.float64)
+        dump_outputs(a.dump_outputs, arrays, suffix=f".rank{rank}" if world > 1 else "")
+        del P, Q, arrays
     kp = None
     if not a.no_profile:  # live per-kernel HIP events over the same number of steps
         m.profile(True)

@@ -15,7 +15,7 @@ for r in $(seq 1 "$reps"); do
     name="${spec%%:*}"; envs="${spec#*:}"
     ( [ "$envs" != "$spec" ] && [ -n "$envs" ] && for kv in ${envs//,/ }; do export "$kv"; done
       case "${BPRMF_DIAG_LIB:-/}" in /*) ;; *) export BPRMF_DIAG_LIB="$R/$BPRMF_DIAG_LIB" ;; esac
-      timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline "$@" \
+      timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline "$@" \
         > "$out/bench_${name}_$r.log" 2>&1 ) || { echo "variant $name rep $r failed"; tail -n 5 "$out/bench_${name}_$r.log"; exit 1; }
     echo "$name $r $(grep '^{' "$out/bench_${name}_$r.log" | python3 -c '
 import json, sys

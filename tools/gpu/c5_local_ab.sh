@@ -10,7 +10,7 @@ for r in $(seq 1 "$reps"); do
   for spec in "$@"; do
     name="${spec%%:*}"; envs="${spec#*:}"
     ( [ "$envs" != "$spec" ] && [ -n "$envs" ] && for kv in ${envs//,/ }; do export "$kv"; done
-      timeout -k 10 500 python3 bench.py $C5 --semantics local --steps 1024 --warmup 256 \
+      timeout -k 10 500 python3 bench.py --full $C5 --semantics local --steps 1024 --warmup 256 \
         --no-cpu-baseline --no-relaxed > "$out/${name}_$r.log" 2>&1 ) || { echo "variant $name failed"; tail -n 5 "$out/${name}_$r.log"; exit 1; }
     python3 -c "
 import json

@@ -19,4 +19,4 @@ else
   step gpu_tests 800 python -u -m pytest tests -m gpu -x -q --timeout 240 --timeout-method thread
 fi &&
 step smoke 120 python -c "import __graft_entry__ as g; g.smoke()" &&
-step bench20 240 python bench.py --steps 20 --warmup 5
+step bench20 240 python bench.py --full --steps 20 --warmup 5

@@ -16,12 +16,12 @@ step() {  # name, timeout, command...
 }
 step gpu_tests 700 python -u -m pytest tests -m gpu -x -q --timeout 240 --timeout-method thread &&
 step smoke 120 python -c "import __graft_entry__ as g; g.smoke()" &&
-step bench20a 240 python bench.py --steps 20 --warmup 5 &&
-step bench20b 240 python bench.py --steps 20 --warmup 5 --no-cpu-baseline &&
-step bench20c 240 python bench.py --steps 20 --warmup 5 --no-cpu-baseline &&
-step bench_defaults 300 python bench.py --no-cpu-baseline --no-relaxed &&
+step bench20a 240 python bench.py --full --steps 20 --warmup 5 &&
+step bench20b 240 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline &&
+step bench20c 240 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline &&
+step bench_defaults 300 python bench.py --full --no-cpu-baseline --no-relaxed &&
 cd /tmp && export TMPDIR=/tmp &&
-step prof 240 rocprofv3 --kernel-trace --stats -d "$out/prof" -o run --output-format csv -- python3 "$R/bench.py" --steps 20 --warmup 5 --no-cpu-baseline &&
+step prof 240 rocprofv3 --kernel-trace --stats -d "$out/prof" -o run --output-format csv -- python3 "$R/bench.py" --full --steps 20 --warmup 5 --no-cpu-baseline &&
 cd "$R" &&
 step pmc_headline 400 bash tools/gpu/pmc.sh "$tag/pmc_h" ml20m_d128_B4096 1 --steps 200 --warmup 20 &&
 step pmc_local 400 bash tools/gpu/pmc.sh "$tag/pmc_l" ml20m_d128_B4096_local 128 --semantics local --steps 1024 --warmup 256

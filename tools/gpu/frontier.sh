@@ -8,7 +8,7 @@ mkdir -p "$out"
 for ls in $periods; do
   timeout -k 10 300 python -u tools/hr_modes.py --which planted,f5 --modes local --seeds 11 --epochs 10 \
     --users-eval 20000 --local-steps "$ls" >> "$out/hr_modes.jsonl" 2>> "$out/hr_modes.err" || { tail -n 20 "$out/hr_modes.err"; exit 1; }
-  timeout -k 10 200 python bench.py --semantics local --local-steps "$ls" --no-cpu-baseline > "$out/bench_ls$ls.log" 2>&1 || { tail -n 5 "$out/bench_ls$ls.log"; exit 1; }
+  timeout -k 10 200 python bench.py --full --semantics local --local-steps "$ls" --no-cpu-baseline > "$out/bench_ls$ls.log" 2>&1 || { tail -n 5 "$out/bench_ls$ls.log"; exit 1; }
   python -c "
 import json
 d=json.loads(open('$out/bench_ls$ls.log').read().strip().splitlines()[-1]); r=d['roofline']

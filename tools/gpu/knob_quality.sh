@@ -12,7 +12,7 @@ for knob in "" "$@"; do
   ( [ -n "$knob" ] && export $knob
     timeout -k 10 300 python -u tools/hr_modes.py --which planted,f5 --modes local --seeds 11 --epochs 10 \
       --users-eval 20000 | sed "s/^{/{\"variant\": \"$variant\", \"knob\": \"$knob\", /" >> "$out/hr_modes.jsonl" 2>> "$out/hr_modes.err" &&
-    timeout -k 10 200 python bench.py --semantics local --no-cpu-baseline > "$out/bench_$variant.log" 2>&1 ) ||
+    timeout -k 10 200 python bench.py --full --semantics local --no-cpu-baseline > "$out/bench_$variant.log" 2>&1 ) ||
     { tail -n 20 "$out/hr_modes.err" "$out/bench_$variant.log"; exit 1; }
   python -c "
 import json

@@ -13,7 +13,7 @@ fac=128
 for ((a = 1; a <= $#; a++)); do [ "${!a}" = "--factor" ] && { b=$((a + 1)); fac="${!b}"; }; done
 cd /tmp && export TMPDIR=/tmp
 for c in FETCH_SIZE WRITE_SIZE; do
-  timeout -s KILL 500 rocprofv3 --pmc $c -d "$O/$c" -o run --output-format csv -- python3 "$R/bench.py" \
+  timeout -s KILL 500 rocprofv3 --pmc $c -d "$O/$c" -o run --output-format csv -- python3 "$R/bench.py" --full \
     --no-cpu-baseline --no-profile --no-relaxed "$@" > "$O/$c.out" 2>&1 || { tail -n 5 "$O/$c.out"; exit 1; }
 done
 cd "$R" && python3 tools/pmc_traffic.py "$key" "$O/FETCH_SIZE" "$O/WRITE_SIZE" --factor "$fac" \

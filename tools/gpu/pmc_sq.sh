@@ -8,7 +8,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 tag=$1; shift
 O=$R/gpurun_out/pmc_sq/$tag
 mkdir -p $O
-prog=("$R/bench.py" --steps 20 --warmup 5 --no-cpu-baseline --no-profile)
+prog=("$R/bench.py" --full --steps 20 --warmup 5 --no-cpu-baseline --no-profile)
 if [ "$1" = "--ncf" ]; then shift; prog=("$R/tools/bench_ncf.py" --no-cpu-baseline --steps 100 --warmup 10); fi
 cd /tmp && export TMPDIR=/tmp
 timeout -s KILL 90 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_INST_LDS SQ_INSTS_VALU -d $O/p1 -o run --output-format csv -- python3 "${prog[@]}" "$@" > $O/p1.out 2>&1 || { tail -5 $O/p1.out; exit 1; }

@@ -13,6 +13,6 @@ out="gpurun_out/$tag"
 mkdir -p "$out"
 [ "$W" -gt 4 ] && export GPU_MAX_HW_QUEUES=1
 timeout -k 10 500 python -m torch.distributed.run --nnodes=1 --nproc-per-node "$W" --master-addr 127.0.0.1 \
-  --master-port $((29600 + W)) bench.py --gpus "$W" --pg-backend gloo --no-cpu-baseline "$@" \
+  --master-port $((29600 + W)) bench.py --full --gpus "$W" --pg-backend gloo --no-cpu-baseline "$@" \
   > "$out/w$W.log" 2>&1 || { grep -h "Error" "$out/w$W.log" | head -n 5; exit 1; }
 grep -h '^{' "$out/w$W.log" | cut -c1-400

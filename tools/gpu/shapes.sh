@@ -9,7 +9,7 @@ ML1M="--users 6040 --items 3706 --positives 575000 --factor 64"
 run() {  # name, timeout, args...
   local n="$1" to="$2"; shift 2
   [[ ",$only," == *",$n,"* ]] || return 0
-  timeout -k 10 "$to" python3 bench.py --no-cpu-baseline --no-relaxed "$@" > "$out/$n.log" 2>&1 || { tail -n 5 "$out/$n.log"; return 1; }
+  timeout -k 10 "$to" python3 bench.py --full --no-cpu-baseline --no-relaxed "$@" > "$out/$n.log" 2>&1 || { tail -n 5 "$out/$n.log"; return 1; }
   python3 -c "
 import json
 d=json.loads(open('$out/$n.log').read().strip().splitlines()[-1]); r=d['roofline']

@@ -18,7 +18,7 @@ for r in $(seq 1 "$reps"); do
   for v in "${variants[@]}"; do
     IFS='|' read -r name envs extra <<< "$v"
     ( for kv in $envs; do export "$kv"; done
-      timeout -k 10 200 python3 bench.py $args $extra > "$out/${name}_$r.log" 2>&1 ) ||
+      timeout -k 10 200 python3 bench.py --full $args $extra > "$out/${name}_$r.log" 2>&1 ) ||
       { echo "$name rep $r failed"; tail -n 5 "$out/${name}_$r.log"; exit 1; }
     echo "$name $r $(grep '^{' "$out/${name}_$r.log" | python3 -c '
 import json, sys

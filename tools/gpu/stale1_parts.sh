@@ -14,7 +14,7 @@ run() {  # name, env, args...
   local n="$1" env="$2"; shift 2
   ( [ -n "$env" ] && export $env
     timeout -k 10 500 rocprofv3 --kernel-trace --stats -d "$out/prof_$n" -o run --output-format csv \
-      -- python3 "$R/bench.py" --sharded --no-cpu-baseline --no-relaxed "$@" > "$out/$n.log" 2>&1 ) ||
+      -- python3 "$R/bench.py" --full --sharded --no-cpu-baseline --no-relaxed "$@" > "$out/$n.log" 2>&1 ) ||
     { tail -n 8 "$out/$n.log"; return 1; }
   grep -h '^{' "$out/$n.log" | python3 -c "
 import json,sys; d=json.loads(sys.stdin.read()); r=d['roofline']

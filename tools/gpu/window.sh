@@ -9,7 +9,7 @@ for w in $wins; do
   export BPRMF_HOGWILD_WINDOW=$w
   timeout -k 10 300 python -u tools/hr_modes.py --which planted,f5 --modes local --seeds 11 --epochs 10 \
     --users-eval 20000 | sed "s/^{/{\"window\": $w, /" >> "$out/hr_modes.jsonl" 2>> "$out/hr_modes.err" || { tail -n 20 "$out/hr_modes.err"; exit 1; }
-  timeout -k 10 200 python bench.py --semantics local --no-cpu-baseline > "$out/bench_w$w.log" 2>&1 || { tail -n 5 "$out/bench_w$w.log"; exit 1; }
+  timeout -k 10 200 python bench.py --full --semantics local --no-cpu-baseline > "$out/bench_w$w.log" 2>&1 || { tail -n 5 "$out/bench_w$w.log"; exit 1; }
   python -c "
 import json
 d=json.loads(open('$out/bench_w$w.log').read().strip().splitlines()[-1]); r=d['roofline']
