@@ -2,7 +2,7 @@
 BPRMFRecommender / util.data_loader.BPRData / util.metrics BPR parts), plus the NCF path of
 SURVEY.md §8f (NCFRecommender / NCFData), the Cython rating-SGD models SVD / RSVD
 (util/matrix_factorization.pyx) BPR-FM (BPRFMRecommender / BPRFMData) and Item2Vec (Item2VecRecommender SGNS /
-BuildCorpus).
+BuildCorpus) and the implicit-feedback ALS model WRMF (WRMFRecommender).
 
 The directory name is not a Python identifier; import it with
     importlib.import_module("recommend-lib_amd")
@@ -28,9 +28,11 @@ from . import bprfm
 from .bprfm import BPRFM, BPRFMData
 from . import item2vec
 from .item2vec import Item2Vec, SGNS, BuildCorpus, PermutedSubsampledCorpus
+from . import wrmf
+from .wrmf import WRMF
 
 BPR = BPRMF  # the reference's class name (BPRMFRecommender.py:28)
 
 __all__ = ["BPRMF", "BPR", "BPRData", "NCF", "NCFData", "ShardedBPRMF", "BprmfError", "metrics",
            "ingest", "load_rate", "load_mat", "SVD", "RSVD", "SVDpp", "BPRFM", "BPRFMData", "Item2Vec", "SGNS", "BuildCorpus",
-           "PermutedSubsampledCorpus", "build", "LIB_PATH"]
+           "PermutedSubsampledCorpus", "WRMF", "build", "LIB_PATH"]

@@ -1,4 +1,4 @@
-"""ctypes binding of libbprmf_amd.so (include/bprmf.h, ncf.h, mf.h, bprfm.h, sgns.h).
+"""ctypes binding of libbprmf_amd.so (include/bprmf.h, ncf.h, mf.h, bprfm.h, sgns.h, wrmf.h).
 
 The HIP library is the only compute path: if it is missing or no GPU is visible, handle creation
 raises — there is no CPU fallback in the product.
@@ -169,6 +169,18 @@ SIGNATURES = {
     "sgns_negatives": [_P, ctypes.c_int32, _P],
     "sgns_lookup": [_P, ctypes.c_int32, _P, _I64, _P],
 }
+# include/wrmf.h (wrmf_config / wrmf_stats: recommend-lib_amd/wrmf.py)
+WRMF_SIGNATURES = {
+    "wrmf_create": [_P, ctypes.POINTER(ctypes.c_void_p)],
+    "wrmf_destroy": [_P],
+    "wrmf_set_train": [_P, _P, _P, _P, _I64],
+    "wrmf_set_weights": [_P, _P, _P],
+    "wrmf_get_weights": [_P, _P, _P],
+    "wrmf_gram": [_P, ctypes.c_int32, _P],
+    "wrmf_sweep": [_P, ctypes.c_int32, _P],
+    "wrmf_fit": [_P, ctypes.c_int32, _P],
+    "wrmf_predict": [_P, _P, _P, _I64, _P],
+}
 RESTYPES = {"bprmf_last_error": ctypes.c_char_p, "bprfm_steps": ctypes.c_int64}
 
 _lib = None
@@ -190,7 +202,7 @@ def load():
         pass
     L = ctypes.CDLL(LIB_PATH)
     diag = bool(os.environ.get("BPRMF_DIAG_LIB"))
-    for name, args in SIGNATURES.items():
+    for name, args in {**SIGNATURES, **WRMF_SIGNATURES}.items():
         f = getattr(L, name, None)
         if f is None:
             # a diagnostic variant may hold a subset (tests/sanitize: the host-only ingestion)
