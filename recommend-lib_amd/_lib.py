@@ -215,6 +215,29 @@ def load():
     return L
 
 
+class Handle:
+    """Owner of one library handle: _open(prefix, cfg) calls <prefix>_create, close() (also at
+    garbage collection) calls <prefix>_destroy."""
+    _h = None
+
+    def _open(self, prefix, cfg):
+        self._L, self._prefix = load(), prefix
+        h = ctypes.c_void_p()
+        check(getattr(self._L, prefix + "_create")(ctypes.byref(cfg), ctypes.byref(h)))
+        self._h = h
+
+    def close(self):
+        if self._h:
+            getattr(self._L, self._prefix + "_destroy")(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001  (interpreter shutdown)
+            pass
+
+
 def next_build_tag():
     """The launch tag the process's next split batch build will carry (test hook)."""
     t = ctypes.c_uint32()

@@ -30,7 +30,7 @@ def _i32(a):
     return np.ascontiguousarray(np.asarray(a).reshape(-1), np.int32)
 
 
-class BPRFM:
+class BPRFM(_lib.Handle):
     """BPRFM(num_features, num_factors, batch_norm, drop_prob) + Adagrad(lr, 1e-8).
 
     drop_prob is the reference's list (drop_prob[0] is the FM dropout; a float is accepted too).
@@ -42,26 +42,12 @@ class BPRFM:
         self.num_features, self.num_factors = int(num_features), int(num_factors)
         self.batch_norm, self.drop_prob = bool(batch_norm), drop_prob
         self.lr, self.max_batch = float(lr), int(max_batch)
-        self._L = _lib.load()
         cfg = BPRFMConfig(num_features=self.num_features, num_factors=self.num_factors,
                           batch_norm=int(self.batch_norm), drop_prob=float(p), lr=self.lr,
                           init_std=float(init_std), max_batch=self.max_batch,
                           seed=int(seed) & (2**64 - 1), device=int(device))
-        h = ctypes.c_void_p()
-        _lib.check(self._L.bprfm_create(ctypes.byref(cfg), ctypes.byref(h)))
-        self._h = h
+        self._open("bprfm", cfg)
         self.last_stats = None
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.bprfm_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001  (interpreter shutdown)
-            pass
 
     # --- state ---
     def state_dict(self):

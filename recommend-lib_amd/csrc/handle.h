@@ -9,16 +9,11 @@
 #include <vector>
 
 #include "../../include/bprmf.h"
+#include "dev.h"
 #include "kernels.h"
 #include "status.h"
 
 namespace bprmf {
-
-#define HIPCHK(x)                                                                           \
-  do {                                                                                      \
-    hipError_t e_ = (x);                                                                    \
-    if (e_ != hipSuccess) return bprmf::fail(BPRMF_E_HIP, "%s: %s", #x, hipGetErrorString(e_)); \
-  } while (0)
 
 // position-independent step graphs (launch_step_graph): a graph of n steps runs the batches and
 // optimizer steps the device cursor d_tbase = {t, k} names, then (advancing variant) advances it
@@ -139,13 +134,6 @@ struct bprmf_handle {
 namespace bprmf {
 
 int set_dev(bprmf_handle* h);
-template <typename T>
-int dalloc(T** p, int64_t count) {
-  *p = nullptr;
-  if (count <= 0) return 0;
-  HIPCHK(hipMalloc((void**)p, sizeof(T) * (size_t)count));
-  return 0;
-}
 hipEvent_t prof_event(bprmf_handle* h);
 // record an event before (begin) / after a launch of `kind` when profiling is on
 struct ProfScope {

@@ -168,7 +168,7 @@ class Item2Vec:
         return self._bound().state_dict()["embedding.ovectors.weight"]
 
 
-class SGNS:
+class SGNS(_lib.Handle):
     """SGNS(embedding, vocab_size, n_negs, weights) + optim.Adam(lr, betas, eps).
 
     train_step(iword, owords) = the loop body (loss, zero_grad, backward, step) and returns the
@@ -181,14 +181,11 @@ class SGNS:
             raise ValueError("vocab_size differs from the embedding's")
         self.embedding, self.vocab_size, self.n_negs = embedding, int(vocab_size), int(n_negs)
         self.context, self.max_batch = int(context), int(max_batch)
-        self._L = _lib.load()
         cfg = SgnsConfig(vocab_size=self.vocab_size, embedding_size=embedding.embedding_size,
                          n_negs=self.n_negs, context=self.context, max_batch=self.max_batch,
                          lr=float(lr), beta1=float(betas[0]), beta2=float(betas[1]), eps=float(eps),
                          seed=int(seed) & (2**64 - 1), device=int(device))
-        h = ctypes.c_void_p()
-        _lib.check(self._L.sgns_create(ctypes.byref(cfg), ctypes.byref(h)))
-        self._h = h
+        self._open("sgns", cfg)
         self.weights = None
         if weights is not None:
             w = np.ascontiguousarray(np.asarray(weights, np.float64).reshape(-1))
@@ -202,17 +199,6 @@ class SGNS:
             _lib.check(self._L.sgns_set_weights(self._h, _lib.ptr(I), _lib.ptr(O)))
         embedding._sgns = self
         self.last_stats = None
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.sgns_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001  (interpreter shutdown)
-            pass
 
     # --- training (:276-287) ---
     def train_examples(self, iwords, owords, nwords=None, batch_size=None):

@@ -45,32 +45,18 @@ def _rows(train_set):
             np.ascontiguousarray(r, np.float64), gm)
 
 
-class _MF:
+class _MF(_lib.Handle):
     _model = MF_SVD
 
-    def _open(self, user_num, item_num, n_factors, variant, lr, reg, device, lr_yj=0.0, reg_yj=0.0):
-        self._L = _lib.load()
+    def _create(self, user_num, item_num, n_factors, variant, lr, reg, device, lr_yj=0.0, reg_yj=0.0):
         cfg = MfConfig(user_num=int(user_num), item_num=int(item_num), n_factors=int(n_factors),
                        model=self._model, variant=int(variant), device=int(device),
                        lr_yj=float(lr_yj), reg_yj=float(reg_yj))
         for x in range(4):
             cfg.lr[x] = float(lr[x])
             cfg.reg[x] = float(reg[x])
-        h = ctypes.c_void_p()
-        _lib.check(self._L.mf_create(ctypes.byref(cfg), ctypes.byref(h)))
-        self._h = h
+        self._open("mf", cfg)
         self.last_stats = None
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.mf_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001  (interpreter shutdown)
-            pass
 
     def _run(self, train_set, P0, Q0, epochs, gm=None):
         u, i, r, mean = _rows(train_set)
@@ -124,9 +110,9 @@ class SVD(_MF):
         self.reg_pu = reg_pu if reg_pu is not None else reg_all
         self.reg_qi = reg_qi if reg_qi is not None else reg_all
         self.random_state, self.verbose = random_state, verbose
-        self._open(user_num, item_num, n_factors, 1 if biased else 0,
-                   (self.lr_bu, self.lr_bi, self.lr_pu, self.lr_qi),
-                   (self.reg_bu, self.reg_bi, self.reg_pu, self.reg_qi), device)
+        self._create(user_num, item_num, n_factors, 1 if biased else 0,
+                     (self.lr_bu, self.lr_bi, self.lr_pu, self.lr_qi),
+                     (self.reg_bu, self.reg_bi, self.reg_pu, self.reg_qi), device)
 
     def fit(self, train_set):
         # :123-126: zero biases, N(init_mean, init_std_dev) tables from numpy's global RNG
@@ -160,7 +146,7 @@ class RSVD(_MF):
         self.lr, self.reg, self.reg2 = lr, reg, reg2
         self.random_state, self.verbose = random_state, verbose
         self.train_when_quiet = train_when_quiet
-        self._open(user_num, item_num, n_factors, version, (lr, 0, 0, 0), (reg, reg2, 0, 0), device)
+        self._create(user_num, item_num, n_factors, version, (lr, 0, 0, 0), (reg, reg2, 0, 0), device)
 
     def fit(self, train_set):
         ui = np.random.normal(self.init_mean, self.init_std_dev, size=(self.user_num, self.n_factors))
@@ -201,10 +187,10 @@ class SVDpp(_MF):
         self.reg_bu, self.reg_bi, self.reg_pu, self.reg_qi, self.reg_yj = (
             pick(reg_bu), pick(reg_bi), pick(reg_pu), pick(reg_qi), pick(reg_yj))
         self.random_state, self.verbose = random_state, verbose
-        self._open(user_num, item_num, n_factors, 1,
-                   (self.lr_bu, self.lr_bi, self.lr_pu, self.lr_qi),
-                   (self.reg_bu, self.reg_bi, self.reg_pu, self.reg_qi), device,
-                   self.lr_yj, self.reg_yj)
+        self._create(user_num, item_num, n_factors, 1,
+                     (self.lr_bu, self.lr_bi, self.lr_pu, self.lr_qi),
+                     (self.reg_bu, self.reg_bi, self.reg_pu, self.reg_qi), device,
+                     self.lr_yj, self.reg_yj)
 
     def fit(self, train_set):
         U, I, k = self.user_num, self.item_num, self.n_factors

@@ -20,7 +20,7 @@ from . import _lib
 MODELS = {"NeuMF-end": 0, "GMF": 1, "MLP": 2}
 
 
-class NCF:
+class NCF(_lib.Handle):
     def __init__(self, user_num, item_num, factor_num=32, num_layers=3, dropout=0.0,
                  model="NeuMF-end", GMF_model=None, MLP_model=None, lr=0.001, batch_size=256,
                  num_ng=4, epochs=20, seed=0, device=0, betas=(0.9, 0.999), eps=1e-8):
@@ -35,16 +35,14 @@ class NCF:
         self.device = int(device)
         self.epoch = 0
         self.history = []
-        L = _lib.load()
         cfg = _lib.NcfConfig(user_num=self.user_num, item_num=self.item_num,
                              factor_num=self.factor_num, num_layers=self.num_layers,
                              model=MODELS[model], batch_size=self.batch_size, num_ng=self.num_ng,
                              lr=float(lr), beta1=float(betas[0]), beta2=float(betas[1]),
                              eps=float(eps), init_std=0.01, seed=int(seed) & (2**64 - 1),
                              device=self.device)
-        h = ctypes.c_void_p()
-        _lib.check(L.ncf_create(ctypes.byref(cfg), ctypes.byref(h)))
-        self._h, self._L = h, L
+        self._open("ncf", cfg)
+        h, L = self._h, self._L
         self._has_train = False
         n = ctypes.c_int32()
         _lib.check(L.ncf_param_count(h, ctypes.byref(n)))
@@ -60,17 +58,6 @@ class NCF:
             _lib.check(L.ncf_param_shape(h, k, ctypes.byref(r), ctypes.byref(c)))
             bias = self.names[k].endswith(".bias")
             self._shapes.append((r.value,) if bias else (r.value, c.value))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.ncf_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     # -- nn.Module surface used by the reference driver ------------------------------------------
     def train(self, mode=True):

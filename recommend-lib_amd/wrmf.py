@@ -51,7 +51,7 @@ def _csr(train_set):
             np.ascontiguousarray(data, np.float64), (int(shape[0]), int(shape[1])))
 
 
-class WRMF:
+class WRMF(_lib.Handle):
     """WRMFRecommender.py:24-62 on the GPU."""
 
     def __init__(self, train_set, lambda_val=0.1, alpha=40, iterations=10, factor_num=20, seed=2019,
@@ -64,14 +64,10 @@ class WRMF:
         self.num_user, self.num_item = U, I
         self.rstate, self._X, self._Y = self.initial_factors(U, I, factor_num, seed)
         self.last_stats = None
-        self._h = None
-        self._L = _lib.load()
         cfg = WrmfConfig(user_num=U, item_num=I, factor_num=int(factor_num), device=int(device),
                          lambda_val=float(lambda_val), gram_mode=GRAM_MODES[gram],
                          heavy_nnz=int(heavy_nnz))
-        h = ctypes.c_void_p()
-        _lib.check(self._L.wrmf_create(ctypes.byref(cfg), ctypes.byref(h)))
-        self._h = h
+        self._open("wrmf", cfg)
         conf = np.ascontiguousarray(alpha * data, np.float64)  # :28 C = alpha * train_set
         _lib.check(self._L.wrmf_set_train(self._h, _lib.ptr(indptr), _lib.ptr(indices),
                                           _lib.ptr(conf), len(indices)))
@@ -84,17 +80,6 @@ class WRMF:
         X = rstate.normal(scale=0.01, size=(num_user, factor_num))
         Y = rstate.normal(scale=0.01, size=(num_item, factor_num))
         return rstate, X, Y
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.wrmf_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001  (interpreter shutdown)
-            pass
 
     def _push(self):
         _lib.check(self._L.wrmf_set_weights(self._h, _lib.ptr(self._X), _lib.ptr(self._Y)))

@@ -1,6 +1,8 @@
 // host_plan_check.cpp — drives the host-only planning logic of libbprmf_amd (csrc/host_plan.cpp:
 // the shard's positive lists behind bprmf_set_train_ex, the sharded runner's geometry, exchange
-// capacity and apply-plan sizes, the IPC blobs' device comparison) under AddressSanitizer +
+// capacity and apply-plan sizes, the IPC blobs' device comparison; csrc/model_plan.cpp: the
+// rating-SGD levels, SVD++ lists, WRMF's CSR sides and launch plans, Item2Vec's noise CDF) under
+// AddressSanitizer +
 // UndefinedBehaviorSanitizer (tests/sanitize/Makefile; run by tests/test_sanitizers.py).
 // Every result is checked against a direct restatement; any sanitizer report aborts the run.
 #include <stdio.h>
@@ -10,6 +12,8 @@
 #include <sys/wait.h>
 #include <unistd.h>
 
+#include <algorithm>
+#include <cmath>
 #include <map>
 #include <random>
 #include <set>
@@ -17,6 +21,7 @@
 
 #include "../../include/bprmf.h"
 #include "../../recommend-lib_amd/csrc/host_plan.h"
+#include "../../recommend-lib_amd/csrc/model_plan.h"
 
 using namespace bprmf;
 
@@ -122,8 +127,262 @@ static void check_tree(std::mt19937_64& g, int64_t U, int64_t I, int64_t maxdeg)
   CHECK(ok);
 }
 
+// train rows for the rating-SGD plans: mode 0 uniform, 1 every row on one user, 2 one item
+static void draw_rows(std::mt19937_64& g, int64_t U, int64_t I, int64_t n, int mode,
+                      std::vector<int32_t>* u, std::vector<int32_t>* it) {
+  u->resize(n);
+  it->resize(n);
+  const int32_t fixed_u = (int32_t)(g() % U), fixed_i = (int32_t)(g() % I);
+  for (int64_t s = 0; s < n; ++s) {
+    (*u)[s] = mode == 1 ? fixed_u : (int32_t)(g() % U);
+    (*it)[s] = mode == 2 ? fixed_i : (int32_t)(g() % I);
+  }
+}
+
+// the dependency levels (mf_level_plan): the rating of sample s is s, so a slot names its sample
+static void check_levels(std::mt19937_64& g, int64_t U, int64_t I, int64_t n, int mode) {
+  std::vector<int32_t> u, it;
+  draw_rows(g, U, I, n, mode, &u, &it);
+  std::vector<double> r(n);
+  for (int64_t s = 0; s < n; ++s) r[s] = (double)s;
+  MfLevelPlan p;
+  const int rc = mf_level_plan(u.data(), it.data(), r.data(), n, U, I, &p);
+  CHECK(rc == 0);
+  if (rc) return;
+  const int64_t L = p.levels;
+  CHECK((int64_t)p.su.size() == n && (int64_t)p.si.size() == n && (int64_t)p.sr.size() == n);
+  CHECK((int64_t)p.loff.size() == L + 1 && p.loff[0] == 0 && p.loff[L] == n);
+  if ((int64_t)p.sr.size() != n || (int64_t)p.loff.size() != L + 1) return;
+  std::vector<int64_t> lvl(n, -1);  // level of each sample, read back through loff
+  bool ok = true, kept = true;
+  for (int64_t l = 0; l < L && ok; ++l) {
+    ok = p.loff[l] < p.loff[l + 1];  // no empty level
+    for (int64_t d = p.loff[l]; d < p.loff[l + 1] && ok; ++d) {
+      const int64_t s = (int64_t)p.sr[d];
+      ok = s >= 0 && s < n && lvl[s] < 0 && p.su[d] == u[s] && p.si[d] == it[s];
+      if (ok) lvl[s] = l;
+      if (d > p.loff[l] && p.sr[d - 1] >= p.sr[d]) kept = false;  // train order within a level
+    }
+  }
+  CHECK(ok);
+  CHECK(kept);
+  if (!ok) return;
+  bool before = true, tight = true;
+  for (int64_t t = 0; t < n; ++t) {
+    int64_t want = 0;  // 1 + max over the earlier samples sharing t's user or item
+    for (int64_t s = 0; s < t; ++s)
+      if (u[s] == u[t] || it[s] == it[t]) {
+        before = before && lvl[s] < lvl[t];
+        want = std::max(want, lvl[s] + 1);
+      }
+    tight = tight && lvl[t] == want;
+  }
+  CHECK(before);
+  CHECK(tight);
+  std::vector<int64_t> hist(L + 1, 0);
+  for (int64_t s = 0; s < n; ++s) hist[lvl[s] + 1]++;
+  for (int64_t l = 0; l < L; ++l) hist[l + 1] += hist[l];
+  CHECK(std::equal(hist.begin(), hist.end(), p.loff.begin()));
+}
+
+// SVD++'s per-user lists (svdpp_plan); dup: the first user's list repeats an item on purpose
+static void check_svdpp(std::mt19937_64& g, int64_t U, int64_t I, int64_t n, int mode, bool dup) {
+  std::vector<int32_t> u, it;
+  draw_rows(g, U, I, n, mode, &u, &it);
+  if (dup && n >= 3) {
+    u[n - 1] = u[0];
+    it[n - 1] = it[0];
+  }
+  SvdppPlan p;
+  const int rc = svdpp_plan(u.data(), it.data(), n, U, I, &p);
+  CHECK(rc == 0);
+  if (rc) return;
+  CHECK((int64_t)p.uoff.size() == U + 1 && (int64_t)p.udup.size() == U);
+  CHECK((int64_t)p.uitems.size() == n && (int64_t)p.uslot.size() == n);
+  if ((int64_t)p.uoff.size() != U + 1 || (int64_t)p.uitems.size() != n || (int64_t)p.uslot.size() != n) return;
+  bool lists = p.uoff[0] == 0, dups = true, slots = true;
+  for (int64_t x = 0; x < U && lists; ++x) {
+    std::vector<int32_t> want;  // x's items in train order
+    for (int64_t s = 0; s < n; ++s)
+      if (u[s] == x) want.push_back(it[s]);
+    lists = p.uoff[x + 1] - p.uoff[x] == (int64_t)want.size() &&
+            std::equal(want.begin(), want.end(), p.uitems.begin() + p.uoff[x]);
+    if (!lists) break;
+    bool repeats = false;
+    for (size_t q = 0; q < want.size(); ++q) {
+      const size_t first = std::find(want.begin(), want.end(), want[q]) - want.begin();
+      repeats = repeats || first != q;
+      slots = slots && p.uslot[p.uoff[x] + q] == (int32_t)first;
+    }
+    dups = dups && p.udup[x] == (repeats ? 1 : 0);
+  }
+  CHECK(lists);
+  CHECK(dups);
+  CHECK(slots);
+  if (dup && n >= 3) CHECK(p.udup[u[0]] == 1);
+}
+
+// one WRMF side against its dense restatement D [rows][cols] (0 = absent), and its launch plan
+static void check_wrmf_side(const WrmfSide& s, const std::vector<std::vector<double>>& D, int64_t rows,
+                            int64_t cols, int32_t heavy) {
+  CHECK(s.rows == rows && (int64_t)s.indptr.size() == rows + 1 && s.indptr[0] == 0);
+  if ((int64_t)s.indptr.size() != rows + 1) return;
+  bool csr = s.indices.size() == s.conf.size() && s.indptr[rows] == (int64_t)s.indices.size();
+  for (int64_t r = 0; r < rows && csr; ++r) {
+    int64_t x = s.indptr[r];
+    for (int64_t c = 0; c < cols && csr; ++c)
+      if (D[r][c] != 0.0) {
+        csr = x < s.indptr[r + 1] && s.indices[x] == c && s.conf[x] == D[r][c];
+        ++x;
+      }
+    csr = csr && x == s.indptr[r + 1];
+  }
+  CHECK(csr);
+  if (!csr) return;
+  auto nnz = [&](int64_t r) { return s.indptr[r + 1] - s.indptr[r]; };
+  std::vector<int32_t> want;  // the light rows by decreasing nnz, ties by row id
+  for (int64_t r = 0; r < rows; ++r)
+    if (nnz(r) <= heavy) want.push_back((int32_t)r);
+  std::sort(want.begin(), want.end(),
+            [&](int32_t a, int32_t b) { return nnz(a) != nnz(b) ? nnz(a) > nnz(b) : a < b; });
+  CHECK(s.order == want);
+  CHECK(s.n_light == (int32_t)s.order.size() && s.n_heavy == (int32_t)s.hrow.size() &&
+        s.n_parts == (int32_t)s.prow.size());
+  CHECK((int64_t)s.order.size() + (int64_t)s.hrow.size() == rows);
+  CHECK(s.hoff.size() == s.hrow.size() + 1 && s.hoff[0] == 0 && s.hoff.back() == (int64_t)s.prow.size());
+  CHECK(s.pbeg.size() == s.prow.size() && s.pend.size() == s.prow.size());
+  if (s.hoff.size() != s.hrow.size() + 1 || s.pbeg.size() != s.prow.size() || s.pend.size() != s.prow.size())
+    return;
+  std::set<int32_t> heavy_rows(s.hrow.begin(), s.hrow.end());
+  bool exact = heavy_rows.size() == s.hrow.size(), tiles = true;
+  for (size_t h = 0; h < s.hrow.size() && exact && tiles; ++h) {
+    const int32_t r = s.hrow[h];
+    exact = r >= 0 && r < rows && nnz(r) > heavy;
+    if (!exact) break;
+    int64_t at = s.indptr[r];  // the parts tile the row in order, `heavy` entries each but the last
+    tiles = s.hoff[h] < s.hoff[h + 1] && s.hoff[h + 1] <= (int64_t)s.prow.size();
+    for (int64_t q = s.hoff[h]; q < s.hoff[h + 1] && tiles; ++q) {
+      const bool last = q + 1 == s.hoff[h + 1];
+      tiles = s.prow[q] == r && s.pbeg[q] == at && s.pend[q] > at &&
+              (last ? s.pend[q] == s.indptr[r + 1] && s.pend[q] - at <= heavy : s.pend[q] - at == heavy);
+      at = s.pend[q];
+    }
+  }
+  CHECK(exact);
+  CHECK(tiles);
+}
+
+static void check_wrmf(std::mt19937_64& g, int64_t U, int64_t I, int fill_pct, int32_t heavy, int one_user) {
+  std::vector<std::vector<double>> D(U, std::vector<double>(I, 0.0)), Dt(I, std::vector<double>(U, 0.0));
+  std::vector<int64_t> indptr(U + 1, 0);
+  std::vector<int32_t> indices;
+  std::vector<double> conf;
+  for (int64_t u = 0; u < U; ++u) {
+    for (int64_t i = 0; i < I; ++i) {
+      if (one_user >= 0 ? u != one_user : (int)(g() % 100) >= fill_pct) continue;
+      const double c = g() % 4 == 0 ? 0.0 : 1.0 + (double)(g() % 1000) / 8.0;  // stored zeros are dropped
+      indices.push_back((int32_t)i);
+      conf.push_back(c);
+      D[u][i] = Dt[i][u] = c;
+    }
+    indptr[u + 1] = (int64_t)indices.size();
+  }
+  WrmfCsrPlan p;
+  const int rc = wrmf_csr_plan(indptr.data(), indices.data(), conf.data(), (int64_t)indices.size(), U, I,
+                               heavy, &p);
+  CHECK(rc == 0);
+  if (rc) return;
+  check_wrmf_side(p.side[0], D, U, I, heavy);
+  check_wrmf_side(p.side[1], Dt, I, U, heavy);  // the exact transpose, rows ascending in a column
+}
+
+static void check_cdf(std::mt19937_64& g, int64_t V) {
+  std::vector<double> w(V);
+  for (int64_t x = 0; x < V; ++x) w[x] = g() % 3 == 0 ? 0.0 : (double)(g() % 100000) / 7.0;
+  w[g() % V] = 5.0;  // not all zero
+  std::vector<float> c;
+  CHECK(sgns_noise_cdf(w.data(), V, &c) == 0);
+  CHECK((int64_t)c.size() == V);
+  if ((int64_t)c.size() != V) return;
+  double tot = 0.0, acc = 0.0;
+  for (int64_t x = 0; x < V; ++x) tot += std::pow(w[x], 0.75);
+  bool sums = true, rises = true;
+  for (int64_t x = 0; x < V; ++x) {
+    acc += std::pow(w[x], 0.75) / tot;
+    if (x + 1 < V) sums = sums && c[x] == (float)acc;
+    if (x) rises = rises && c[x - 1] <= c[x];
+  }
+  CHECK(sums);
+  CHECK(rises);
+  CHECK(c[V - 1] == 2.0f);
+}
+
 int main() {
   std::mt19937_64 g(20261017);
+  // the sibling models' plans (model_plan.cpp): empty input, one user, one item, every row on one
+  // user or one item, random small shapes
+  check_levels(g, 1, 1, 0, 0);
+  check_levels(g, 1, 7, 30, 0);
+  check_levels(g, 7, 1, 30, 0);
+  check_svdpp(g, 1, 1, 0, 0, false);
+  check_svdpp(g, 1, 5, 40, 0, true);
+  check_svdpp(g, 4, 6, 3, 0, true);
+  for (int rep = 0; rep < 60; ++rep) {
+    const int64_t U = 1 + (int64_t)(g() % 12), I = 1 + (int64_t)(g() % 12), n = (int64_t)(g() % 201);
+    check_levels(g, U, I, n, rep % 3);
+    check_svdpp(g, U, I, n, rep % 3, rep % 2 == 0);
+  }
+  {  // an id out of range, at either end of either column: refused, with nothing half-built
+    const int32_t us[4][3] = {{0, 5, 1}, {0, -1, 1}, {0, 1, 2}, {0, 1, 2}};
+    const int32_t is[4][3] = {{1, 1, 1}, {1, 1, 1}, {1, 4, 1}, {1, 1, -1}};
+    const double r[3] = {1.0, 2.0, 3.0};
+    for (int c = 0; c < 4; ++c) {
+      MfLevelPlan p;
+      CHECK(mf_level_plan(us[c], is[c], r, 3, 5, 4, &p) == BPRMF_E_RANGE);
+      CHECK(p.su.empty() && p.si.empty() && p.sr.empty() && p.loff.empty() && p.levels == 0);
+      SvdppPlan q;
+      CHECK(svdpp_plan(us[c], is[c], 3, 5, 4, &q) == BPRMF_E_RANGE);
+      CHECK(q.uoff.empty() && q.uitems.empty() && q.udup.empty() && q.uslot.empty());
+    }
+  }
+  for (int32_t heavy : {1, 3, 1000}) {
+    check_wrmf(g, 1, 1, 0, heavy, -1);   // no entry at all
+    check_wrmf(g, 1, 9, 100, heavy, 0);  // one user
+    check_wrmf(g, 8, 11, 100, heavy, 5); // every entry on one user
+    for (int rep = 0; rep < 20; ++rep)
+      check_wrmf(g, 1 + (int64_t)(g() % 12), 1 + (int64_t)(g() % 12), (int)(g() % 101), heavy, -1);
+  }
+  {  // wrmf_set_train's documented BPRMF_E_RANGE cases; 2 users, 4 items
+    struct Bad {
+      int64_t indptr[3];
+      int32_t indices[3];
+      int64_t nnz;
+    };
+    const Bad bad[] = {
+        {{1, 2, 3}, {0, 1, 2}, 3},   // indptr does not start at 0
+        {{0, 2, 2}, {0, 1, 2}, 3},   // ... or end at nnz
+        {{0, 3, 2}, {0, 1, 2}, 2},   // a row running past nnz
+        {{0, 2, 1}, {0, 1, 2}, 1},   // indptr decreases
+        {{0, 2, 3}, {0, 4, 2}, 3},   // column past the end
+        {{0, 2, 3}, {-1, 1, 2}, 3},  // negative column
+        {{0, 2, 3}, {1, 1, 2}, 3},   // a repeated column
+        {{0, 3, 3}, {0, 2, 1}, 3},   // columns not increasing
+    };
+    const double conf[3] = {1.0, 2.0, 3.0};
+    for (const Bad& b : bad) {
+      WrmfCsrPlan p;
+      CHECK(wrmf_csr_plan(b.indptr, b.indices, conf, b.nnz, 2, 4, 3, &p) == BPRMF_E_RANGE);
+      CHECK(p.side[0].indptr.empty() && p.side[1].indptr.empty() && p.side[0].hoff.empty());
+    }
+  }
+  for (int64_t V : {2LL, 3LL, 12LL, 200LL}) check_cdf(g, V);
+  {  // a negative weight, a NaN, all zeros
+    std::vector<float> c(3, 1.f);
+    const double neg[3] = {1.0, -0.5, 2.0}, nan_[3] = {1.0, std::nan(""), 2.0}, zero[3] = {0.0, 0.0, 0.0};
+    CHECK(sgns_noise_cdf(neg, 3, &c) == BPRMF_E_INVALID && c.empty());
+    CHECK(sgns_noise_cdf(nan_, 3, &c) == BPRMF_E_INVALID && c.empty());
+    CHECK(sgns_noise_cdf(zero, 3, &c) == BPRMF_E_INVALID && c.empty());
+  }
   // the sampler's search trees: empty users, one node, 2-4 levels (up to 16^3 + positives)
   check_tree(g, 50, 40, 16);
   check_tree(g, 200, 3000, 300);

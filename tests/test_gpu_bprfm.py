@@ -213,3 +213,22 @@ def test_factor_widths_against_oracle(rl, k, bn):
         assert got == pytest.approx(want, rel=LOSS_RTOL)
     check_params(m.state_dict(), st.E, st.b, st.bias_,
                  *((st.gamma, st.beta, st.run_mean, st.run_var) if bn else ()))
+
+
+def test_triplet_chunk_regrows_between_calls(rl):
+    """One model trains calls of 8, 50 and 8 triplets in batches of 16: the uploaded chunk grows
+    for the second call and is reused, larger than needed, by the third."""
+    g = np.random.default_rng(8)
+    U, I, k, B = 15, 25, 5, 16
+    E = (0.01 * g.standard_normal((U + I, k))).astype(np.float32)
+    m = rl.BPRFM(U + I, k, True, [0.0], lr=0.05, max_batch=B)
+    m.load_state_dict({"embeddings.weight": E})
+    st = O.State(E, np.zeros(U + I), np.zeros(1), np.ones(k), np.zeros(k))
+    for n in (8, 50, 8):
+        u, i, j = g.integers(0, U, n), U + g.integers(0, I, n), U + g.integers(0, I, n)
+        want = sum(O.step(st, 0, u[b:b + B], i[b:b + B], j[b:b + B], 0.05) for b in range(0, n, B))
+        got = m.train_triplets(u, i, j, batch_size=B)
+        assert got == pytest.approx(want, rel=LOSS_RTOL)
+    assert m.steps == 1 + 4 + 1
+    check_params(m.state_dict(), st.E, st.b, st.bias_, st.gamma, st.beta, st.run_mean, st.run_var,
+                 outliers=True)

@@ -102,3 +102,52 @@ def test_zero_epochs_and_empty_train_set(rl):
     e = rl.SVD(5, 6, n_factors=3, n_epochs=2, verbose=False)
     e.fit(pd.DataFrame({"user": np.zeros(0, int), "item": np.zeros(0, int), "rating": np.zeros(0)}))
     assert e.last_stats["samples"] == 0
+
+
+def _small_sets():
+    """A: 10 rows, B: 60 rows over 5 users x 4 items (B has many more levels than A)."""
+    g = np.random.default_rng(11)
+    return [pd.DataFrame({"user": g.integers(0, 5, n), "item": g.integers(0, 4, n),
+                          "rating": g.integers(1, 6, n).astype(np.float64)}) for n in (10, 60)]
+
+
+REFIT = {"SVD": (lambda rl: rl.SVD(5, 4, n_factors=3, n_epochs=2, verbose=False),
+                 ("pu", "qi", "bu", "bi")),
+         "RSVD": (lambda rl: rl.RSVD(5, 4, n_factors=3, n_epochs=2, verbose=False,
+                                     train_when_quiet=True), ("ui", "vj", "ci", "dj"))}
+
+
+def fit_tables(m, df, names, seed=7):
+    np.random.seed(seed)
+    m.fit(df)
+    return [getattr(m, k).copy() for k in names]
+
+
+@pytest.mark.parametrize("kind", sorted(REFIT))
+def test_refit_on_one_handle_replaces_the_train_set(rl, kind):
+    """fit(A), fit(B), fit(A) on one handle: a larger set and then a smaller one replace the
+    sample buffers and the level count together."""
+    make, names = REFIT[kind]
+    A, B = _small_sets()
+    m = make(rl)
+    first = fit_tables(m, A, names)
+    second = fit_tables(m, B, names)
+    third = fit_tables(m, A, names)
+    fresh = fit_tables(make(rl), B, names)
+    for a, b in zip(third, first):
+        assert np.array_equal(a, b)
+    for a, b in zip(second, fresh):
+        assert np.array_equal(a, b)
+
+
+def test_failed_set_train_keeps_the_previous_set(rl):
+    A, _ = _small_sets()
+    m = rl.SVD(5, 4, n_factors=3, n_epochs=2, verbose=False)
+    np.random.seed(7)
+    m.fit(A)
+    before = m.predict_batch(A.user.values, A.item.values)
+    bad = A.copy()
+    bad.loc[3, "item"] = 4  # one item out of range
+    with pytest.raises(ValueError):
+        m.fit(bad)
+    assert np.array_equal(m.predict_batch(A.user.values, A.item.values), before)

@@ -171,3 +171,25 @@ def test_embedding_widths_against_oracle(rl, E, C, n):
     sd = s.state_dict()
     np.testing.assert_allclose(sd["embedding.ivectors.weight"], st.I, rtol=0, atol=PARAM_ATOL)
     np.testing.assert_allclose(sd["embedding.ovectors.weight"], st.O, rtol=0, atol=PARAM_ATOL)
+
+
+def test_example_chunk_regrows_between_calls(rl):
+    """One model trains calls of 8, 50 and 8 examples in batches of 16: the uploaded chunk grows
+    for the second call and is reused, larger than needed, by the third."""
+    import torch
+    g = np.random.default_rng(12)
+    V, E, C, n, B = 40, 5, 4, 3, 16
+    torch.manual_seed(6)
+    m = rl.Item2Vec(V, E)
+    s = rl.SGNS(m, V, n_negs=n, context=C, max_batch=B)
+    st = O.State(*m._init)
+    for N in (8, 50, 8):
+        iw, ow = g.integers(1, V, N), g.integers(0, V, (N, C))
+        nw = g.integers(0, V - 1, (N, C * n))
+        want = sum(O.step(st, iw[b:b + B], ow[b:b + B], nw[b:b + B]) for b in range(0, N, B))
+        got = s.train_examples(iw, ow, nw, batch_size=B)
+        assert got == pytest.approx(want, rel=LOSS_RTOL)
+    assert s.steps == 1 + 4 + 1
+    sd = s.state_dict()
+    np.testing.assert_allclose(sd["embedding.ivectors.weight"], st.I, rtol=0, atol=PARAM_ATOL)
+    np.testing.assert_allclose(sd["embedding.ovectors.weight"], st.O, rtol=0, atol=PARAM_ATOL)

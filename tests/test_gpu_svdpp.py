@@ -88,3 +88,26 @@ def test_bad_codes_and_empty(rl):
                                [m.predict(4, 5), m.predict(0, 1)], rtol=PRED_RTOL)
     with pytest.raises(ValueError):
         m.predict_batch(np.array([0]), np.array([6]))
+
+
+def test_refit_on_one_handle_replaces_the_train_set(rl):
+    """fit(A), fit(B), fit(A) on one handle: the samples and the per-user lists are replaced
+    together, by a larger set and then by a smaller one."""
+    g = np.random.default_rng(11)
+    A, B = [pd.DataFrame({"user": g.integers(0, 5, n), "item": g.integers(0, 4, n),
+                          "rating": g.integers(1, 6, n).astype(np.float64)}) for n in (10, 60)]
+    names = ("pu", "qi", "yj", "bu", "bi")
+
+    def fit_tables(m, df):
+        np.random.seed(7)
+        m.fit(df)
+        return [getattr(m, k).copy() for k in names]
+
+    make = lambda: rl.SVDpp(5, 4, n_factors=3, n_epochs=2, verbose=False)  # noqa: E731
+    m = make()
+    first, second, third = fit_tables(m, A), fit_tables(m, B), fit_tables(m, A)
+    fresh = fit_tables(make(), B)
+    for a, b in zip(third, first):
+        np.testing.assert_array_equal(a, b)
+    for a, b in zip(second, fresh):
+        np.testing.assert_array_equal(a, b)

@@ -285,3 +285,35 @@ def test_any_factor_count_solves_within_the_backward_error_bound(rl, d):
         ri = residual_ratios(conf_t, X1, Gx, LAMBDA, [Y1], b_terms=True)[0]
         print(f"d={d} heavy_nnz={heavy}: max residual / bound users {ru.max():.4f} items {ri.max():.4f}")
         assert (ru <= 1.0).all() and (ri <= 1.0).all()
+
+
+def test_predict_staging_regrows_and_a_failed_set_train_keeps_the_train_set(rl):
+    """predict_batch with 1, 300 and 2 pairs on one handle (the staging grows once and is then
+    reused); a refused wrmf_set_train on that handle leaves the previous train set whole."""
+    g = np.random.default_rng(3)
+    U, I, d = 6, 5, 4
+    dense = g.integers(1, 6, (U, I)) * (g.random((U, I)) < 0.6)
+    dense[2] = 0  # an empty user
+    indptr = np.concatenate([[0], np.cumsum((dense != 0).sum(1))]).astype(np.int64)
+    indices = np.nonzero(dense)[1].astype(np.int32)
+    csr = (indptr, indices, dense[dense != 0].astype(np.float64), (U, I))
+    make = lambda: rl.WRMF(csr, lambda_val=LAMBDA, alpha=ALPHA, iterations=2, factor_num=d, seed=SEED)  # noqa: E731
+    m = make().fit()
+    X, Y = m.factors()
+    for n in (1, 300, 2):
+        us, it = g.integers(0, U, n), g.integers(0, I, n)
+        np.testing.assert_allclose(m.predict_batch(us, it), np.einsum("nd,nd->n", X[us], Y[it]),
+                                   rtol=1e-12, atol=0)
+    b = int(np.argmax(np.diff(indptr) >= 2))  # a row with two entries: swap them
+    bad = indices.copy()
+    bad[indptr[b]], bad[indptr[b] + 1] = indices[indptr[b] + 1], indices[indptr[b]]
+    conf = np.ascontiguousarray(ALPHA * csr[2])
+    with pytest.raises(ValueError, match="strictly increasing"):
+        rl._lib.check(m._L.wrmf_set_train(m._h, rl._lib.ptr(indptr), rl._lib.ptr(bad),
+                                          rl._lib.ptr(conf), len(bad)))
+    m.fit()
+    fresh = make().fit().fit()
+    for got, want in zip(m.factors(), fresh.factors()):
+        assert np.array_equal(got, want)
+    m.close()
+    fresh.close()
