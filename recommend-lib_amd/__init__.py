@@ -2,7 +2,9 @@
 BPRMFRecommender / util.data_loader.BPRData / util.metrics BPR parts), plus the NCF path of
 SURVEY.md §8f (NCFRecommender / NCFData), the Cython rating-SGD models SVD / RSVD
 (util/matrix_factorization.pyx) BPR-FM (BPRFMRecommender / BPRFMData) and Item2Vec (Item2VecRecommender SGNS /
-BuildCorpus) and the implicit-feedback ALS model WRMF (WRMFRecommender).
+BuildCorpus), the implicit-feedback ALS model WRMF (WRMFRecommender) and the item-item elastic
+net SLIM (SLiMRecommender with util/slim.pyx: Gram matrix on i8 MFMA, coordinate descent in f64,
+bit-identical to the compiled reference).
 
 The directory name is not a Python identifier; import it with
     importlib.import_module("recommend-lib_amd")
@@ -30,9 +32,11 @@ from . import item2vec
 from .item2vec import Item2Vec, SGNS, BuildCorpus, PermutedSubsampledCorpus
 from . import wrmf
 from .wrmf import WRMF
+from . import slim
+from .slim import SLIM
 
 BPR = BPRMF  # the reference's class name (BPRMFRecommender.py:28)
 
 __all__ = ["BPRMF", "BPR", "BPRData", "NCF", "NCFData", "ShardedBPRMF", "BprmfError", "metrics",
            "ingest", "load_rate", "load_mat", "SVD", "RSVD", "SVDpp", "BPRFM", "BPRFMData", "Item2Vec", "SGNS", "BuildCorpus",
-           "PermutedSubsampledCorpus", "WRMF", "build", "LIB_PATH"]
+           "PermutedSubsampledCorpus", "WRMF", "SLIM", "build", "LIB_PATH"]

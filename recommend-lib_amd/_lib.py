@@ -1,4 +1,5 @@
-"""ctypes binding of libbprmf_amd.so (include/bprmf.h, ncf.h, mf.h, bprfm.h, sgns.h, wrmf.h).
+"""ctypes binding of libbprmf_amd.so (include/bprmf.h, ncf.h, mf.h, bprfm.h, sgns.h, wrmf.h,
+slim.h).
 
 The HIP library is the only compute path: if it is missing or no GPU is visible, handle creation
 raises — there is no CPU fallback in the product.
@@ -181,6 +182,20 @@ WRMF_SIGNATURES = {
     "wrmf_fit": [_P, ctypes.c_int32, _P],
     "wrmf_predict": [_P, _P, _P, _I64, _P],
 }
+# include/slim.h (slim_config / slim_stats: recommend-lib_amd/slim.py)
+SLIM_SIGNATURES = {
+    "slim_create": [_P, ctypes.POINTER(ctypes.c_void_p)],
+    "slim_destroy": [_P],
+    "slim_set_train": [_P, _P, _P, _I64],
+    "slim_gram": [_P, _P],
+    "slim_gram_seconds": [_P, ctypes.POINTER(ctypes.c_double)],
+    "slim_fit": [_P, ctypes.c_double, ctypes.c_double, ctypes.c_int32, ctypes.c_int32,
+                 ctypes.c_double, _I64, _I64, _P],
+    "slim_get_weights": [_P, _I64, _I64, _P],
+    "slim_score": [_P, _P, _P, _I64, _P],
+    "slim_score_rows": [_P, _P, _I64, _P],
+    "slim_topk_lists": [_P, _P, _P, _P, _I64, ctypes.c_int32, _P, _P],
+}
 RESTYPES = {"bprmf_last_error": ctypes.c_char_p, "bprfm_steps": ctypes.c_int64}
 
 _lib = None
@@ -202,7 +217,7 @@ def load():
         pass
     L = ctypes.CDLL(LIB_PATH)
     diag = bool(os.environ.get("BPRMF_DIAG_LIB"))
-    for name, args in {**SIGNATURES, **WRMF_SIGNATURES}.items():
+    for name, args in {**SIGNATURES, **WRMF_SIGNATURES, **SLIM_SIGNATURES}.items():
         f = getattr(L, name, None)
         if f is None:
             # a diagnostic variant may hold a subset (tests/sanitize: the host-only ingestion)

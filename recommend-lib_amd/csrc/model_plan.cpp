@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <new>
 #include <numeric>
 #include <utility>
 
@@ -185,6 +186,89 @@ int sgns_noise_cdf(const double* weights, int64_t vocab, std::vector<float>* cdf
   }
   c[V - 1] = 2.0f;  // every u in [0, 1) lands
   *cdf = std::move(c);
+  return 0;
+}
+
+static int slim_plan_build(const int32_t* users, const int32_t* items, int64_t n, int64_t user_num,
+                           int64_t item_num, SlimPlan* out) {
+  const int64_t U = user_num, I = item_num;
+  if (U < 0 || I < 0 || n < 0 || U >= INT32_MAX - kSlimTile || I >= INT32_MAX - kSlimTile)
+    return fail(BPRMF_E_UNSUPPORTED, "user_num and item_num must be in [0, 2^31 - %lld)",
+                (long long)(kSlimTile + 1));
+  // counting sort by user, then the items of every user sorted and made unique
+  std::vector<int64_t> off(U + 1, 0);
+  for (int64_t s = 0; s < n; ++s) {
+    const int32_t u = users[s], i = items[s];
+    if (u < 0 || u >= U || i < 0 || i >= I)
+      return fail(BPRMF_E_RANGE, "train pair %lld = (%d, %d) out of range", (long long)s, u, i);
+    off[u + 1]++;
+  }
+  for (int64_t u = 0; u < U; ++u) off[u + 1] += off[u];
+  std::vector<int32_t> list(n);
+  {
+    std::vector<int64_t> pos(off.begin(), off.end() - 1);
+    for (int64_t s = 0; s < n; ++s) list[pos[users[s]]++] = items[s];
+  }
+  std::vector<int64_t> indptr(U + 1, 0);
+  std::vector<int32_t> indices, rows;
+  indices.reserve(n);
+  rows.reserve(n);
+  for (int64_t u = 0; u < U; ++u) {
+    auto b = list.begin() + off[u], e = list.begin() + off[u + 1];
+    std::sort(b, e);
+    e = std::unique(b, e);
+    indices.insert(indices.end(), b, e);
+    rows.insert(rows.end(), (size_t)(e - b), (int32_t)u);
+    indptr[u + 1] = (int64_t)indices.size();
+  }
+  const int64_t p_pad = (I + kSlimTile - 1) / kSlimTile * kSlimTile;
+  const int64_t k_pad = (U + kSlimTile - 1) / kSlimTile * kSlimTile;
+  if (k_pad && p_pad > INT64_MAX / k_pad)
+    return fail(BPRMF_E_UNSUPPORTED, "the dense operand's size overflows");
+  out->indptr = std::move(indptr);
+  out->indices = std::move(indices);
+  out->rows = std::move(rows);
+  out->p_pad = p_pad;
+  out->k_pad = k_pad;
+  out->operand_bytes = p_pad * k_pad;
+  return 0;
+}
+
+int slim_plan(const int32_t* users, const int32_t* items, int64_t n, int64_t user_num,
+              int64_t item_num, SlimPlan* out) {
+  *out = SlimPlan();
+  try {  // the vectors hold user_num + 1 and n entries: no exception may cross the C ABI
+    return slim_plan_build(users, items, n, user_num, item_num, out);
+  } catch (const std::bad_alloc&) {
+    *out = SlimPlan();
+    return fail(BPRMF_E_UNSUPPORTED, "out of host memory while planning %lld pairs of %lld users",
+                (long long)n, (long long)user_num);
+  }
+}
+
+int slim_check_ids(const int32_t* users, const int32_t* items, int64_t n, int64_t user_num,
+                   int64_t item_num) {
+  for (int64_t x = 0; x < n; ++x) {
+    if (users[x] < 0 || users[x] >= user_num)
+      return fail(BPRMF_E_RANGE, "user %lld = %d out of range", (long long)x, users[x]);
+    if (items && (items[x] < 0 || items[x] >= item_num))
+      return fail(BPRMF_E_RANGE, "pair %lld = (%d, %d) out of range", (long long)x, users[x], items[x]);
+  }
+  return 0;
+}
+
+int slim_check_lists(const int32_t* users, const int64_t* offsets, const int32_t* items,
+                     int64_t n_users, int64_t user_num, int64_t item_num) {
+  if (n_users <= 0) return 0;
+  if (offsets[0] < 0) return fail(BPRMF_E_INVALID, "offsets must start at >= 0");
+  for (int64_t r = 0; r < n_users; ++r) {
+    if (users[r] < 0 || users[r] >= user_num)
+      return fail(BPRMF_E_RANGE, "user %lld = %d out of range", (long long)r, users[r]);
+    if (offsets[r + 1] < offsets[r]) return fail(BPRMF_E_INVALID, "offsets must not decrease");
+  }
+  for (int64_t q = offsets[0]; q < offsets[n_users]; ++q)
+    if (items[q] < 0 || items[q] >= item_num)
+      return fail(BPRMF_E_RANGE, "candidate %lld = %d out of range", (long long)q, items[q]);
   return 0;
 }
 

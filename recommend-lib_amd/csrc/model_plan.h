@@ -1,6 +1,7 @@
 // model_plan.h — the host-only (no HIP) planning logic of the sibling model paths: the rating-SGD
 // dependency levels and SVD++ user lists (mf_capi.cpp), WRMF's two CSR sides with their launch
-// plans (wrmf_capi.cpp) and Item2Vec's noise CDF (sgns_capi.cpp).  Like host_plan.h it stays out
+// plans (wrmf_capi.cpp), Item2Vec's noise CDF (sgns_capi.cpp) and SLIM's pair validation, CSR and
+// operand geometry (slim_capi.cpp).  Like host_plan.h it stays out
 // of the HIP translation units so tests/sanitize builds it under AddressSanitizer +
 // UndefinedBehaviorSanitizer and checks it against restatements.  Every function returns 0 or a
 // bprmf_status; `out` is complete only on success and empty otherwise.
@@ -57,5 +58,27 @@ int wrmf_csr_plan(const int64_t* indptr, const int32_t* indices, const double* c
 // and stored as float, the last entry 2.0f so that every u in [0, 1) lands.  BPRMF_E_INVALID: a
 // negative or NaN weight, weights summing to 0.
 int sgns_noise_cdf(const double* weights, int64_t vocab, std::vector<float>* cdf);
+
+// SLIM (slim_set_train): A as CSR with the items of a user ascending and duplicates collapsed
+// (A[u, i] = 1), `rows` = the user of every kept entry, and the geometry of the dense i8 operand
+// A^T [p_pad, k_pad]: item-major, the user (K) dimension contiguous, both padded to the MFMA tile.
+// BPRMF_E_RANGE: an id out of range; BPRMF_E_UNSUPPORTED: sizes past int32 or an operand whose
+// byte count overflows, or host memory that runs out while the plan is built.
+constexpr int64_t kSlimTile = 128;  // k_pad and p_pad are multiples of it (k_gram's block)
+struct SlimPlan {
+  std::vector<int64_t> indptr;
+  std::vector<int32_t> indices, rows;
+  int64_t p_pad = 0, k_pad = 0, operand_bytes = 0;
+};
+int slim_plan(const int32_t* users, const int32_t* items, int64_t n, int64_t user_num,
+              int64_t item_num, SlimPlan* out);
+// slim_score / slim_score_rows arguments: BPRMF_E_RANGE for an id out of range.  `items` null:
+// users only.
+int slim_check_ids(const int32_t* users, const int32_t* items, int64_t n, int64_t user_num,
+                   int64_t item_num);
+// slim_topk_lists arguments: BPRMF_E_RANGE for an id out of range, BPRMF_E_INVALID for offsets
+// that do not start at >= 0 or decrease.  `items` may be null when no list has any.
+int slim_check_lists(const int32_t* users, const int64_t* offsets, const int32_t* items,
+                     int64_t n_users, int64_t user_num, int64_t item_num);
 
 }  // namespace bprmf
