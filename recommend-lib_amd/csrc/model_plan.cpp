@@ -272,4 +272,26 @@ int slim_check_lists(const int32_t* users, const int64_t* offsets, const int32_t
   return 0;
 }
 
+int ncf_catch_tables(double lr, double b1, double b2, int terms, std::vector<float>* step,
+                     std::vector<float>* pw) {
+  step->clear();
+  pw->clear();
+  if (!(b1 >= 0.0 && b1 < 1.0) || !(b2 >= 0.0 && b2 < 1.0) || terms < 0)
+    return fail(BPRMF_E_INVALID, "bad Adam hyper-parameters");
+  int64_t n = 1;
+  while (n < (1 << 22) && (std::pow(b1, (double)n) > 0x1p-26 || std::pow(b2, (double)n) > 0x1p-26)) n *= 2;
+  std::vector<float> st(2 * (size_t)n), p(2 * (size_t)terms);
+  for (int64_t s = 1; s <= n; ++s) {
+    st[2 * (s - 1)] = (float)(lr / (1.0 - std::pow(b1, (double)s)));
+    st[2 * (s - 1) + 1] = (float)(1.0 / std::sqrt(1.0 - std::pow(b2, (double)s)));
+  }
+  for (int j = 1; j <= terms; ++j) {
+    p[2 * (j - 1)] = (float)std::pow(b1, (double)j);
+    p[2 * (j - 1) + 1] = (float)std::pow(b2, 0.5 * j);
+  }
+  *step = std::move(st);
+  *pw = std::move(p);
+  return 0;
+}
+
 }  // namespace bprmf

@@ -1,8 +1,8 @@
 // model_plan.h — the host-only (no HIP) planning logic of the sibling model paths: the rating-SGD
 // dependency levels and SVD++ user lists (mf_capi.cpp), WRMF's two CSR sides with their launch
-// plans (wrmf_capi.cpp), Item2Vec's noise CDF (sgns_capi.cpp) and SLIM's pair validation, CSR and
-// operand geometry (slim_capi.cpp).  Like host_plan.h it stays out
-// of the HIP translation units so tests/sanitize builds it under AddressSanitizer +
+// plans (wrmf_capi.cpp), Item2Vec's noise CDF (sgns_capi.cpp), SLIM's pair validation, CSR and
+// operand geometry (slim_capi.cpp) and NCF's Adam catch-up tables (ncf_capi.cpp).  Like host_plan.h
+// it stays out of the HIP translation units so tests/sanitize builds it under AddressSanitizer +
 // UndefinedBehaviorSanitizer and checks it against restatements.  Every function returns 0 or a
 // bprmf_status; `out` is complete only on success and empty otherwise.
 #pragma once
@@ -80,5 +80,13 @@ int slim_check_ids(const int32_t* users, const int32_t* items, int64_t n, int64_
 // that do not start at >= 0 or decrease.  `items` may be null when no list has any.
 int slim_check_lists(const int32_t* users, const int64_t* offsets, const int32_t* items,
                      int64_t n_users, int64_t user_num, int64_t item_num);
+
+// NCF (ncf_create): the tables of the zero-gradient Adam steps a row catches up on (k_ncf_catch_up),
+// in double as the step's own AdamArgs, as interleaved float pairs.  step: torch's (step_size(s),
+// 1 / bc2_sqrt(s)) for s = 1 .. n, n the smallest power of two with b1^n and b2^n <= 2^-26 (past it
+// f32 cannot tell the bias corrections from 1: the pair is (lr, 1)), capped at 2^22.  pw: (b1^j,
+// b2^(j/2)) for j = 1 .. terms.  BPRMF_E_INVALID: a beta outside [0, 1) or terms < 0.
+int ncf_catch_tables(double lr, double b1, double b2, int terms, std::vector<float>* step,
+                     std::vector<float>* pw);
 
 }  // namespace bprmf

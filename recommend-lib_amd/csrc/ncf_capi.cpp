@@ -13,16 +13,22 @@
 // (k_ncf_rows; the last step of a call runs it alone, k_ncf_adam_rows).  Every read of the
 // tables from outside a step (predict, get / set_param) first brings the rows it reads to the
 // current step, so every observable value is torch's dense Adam.
-#include <hip/hip_runtime.h>
+// Every device array is a DevBuf (dev.h) of the handle, freed when the handle is deleted; the
+// structs the kernels take (Params, Grads, Acts, RowSides, the jobs) are views filled from those
+// owners once, in ncf_create.  A failed ncf_create leaves nothing behind.  After a failed
+// ncf_set_train the handle holds the previous train set whole.
 #include <string.h>
 
 #include <algorithm>
 #include <cmath>
-#include <string>
+#include <memory>
+#include <utility>
 #include <vector>
 
 #include "../../include/ncf.h"
-#include "handle.h"
+#include "dev.h"
+#include "host_plan.h"
+#include "model_plan.h"
 #include "ncf_kernels.h"
 
 using namespace bprmf;
@@ -30,59 +36,57 @@ using namespace bprmf::ncf;
 
 namespace {
 constexpr int kChunk = 1 << 20;  // sampled samples per sampler launch
-}
+struct TrainSet {                // the positives in input order and their sorted, de-duplicated CSR
+  DevBuf<int32_t> pos_u, pos_i, indices;
+  DevBuf<int64_t> indptr;
+  int64_t n = 0;
+};
+}  // namespace
 
 struct ncf_handle {
   ncf_config cfg;
+  Lane lane;
   Dims D{};
+  // owners
+  DevBuf<float> emb[4], emb_m[4], emb_v[4];  // Pg, Qg, Pm, Qm and their Adam moments
+  DevBuf<float> grad[4];                     // their dense gradient rows
+  DevBuf<int32_t> touch[2];                  // users, items: the last step that gathered each row
+  DevBuf<int32_t> cur[2];        // step each row's p, m, v are current at (-1: never touched)
+  DevBuf<float2> d_step, d_pw;   // catch-up tables (CatchArgs)
+  DevBuf<float> flat[2], wt[2];  // flat tower + predict block and its transposed weights, two copies
+  DevBuf<float> Fm, Fv, acts;    // the block's moments; training activations, max_blocks * 16 rows
+  DevBuf<NcfJob> d_jobs;
+  TrainSet train;
+  DevBuf<int32_t> d_u, d_i;  // sample chunk; d_y, allocated last, carries its capacity
+  DevBuf<float> d_y;
+  DevBuf<double> d_loss;
+  DevBuf<int32_t> d_err;
+  // views into the owners
   Params P{};
   Grads G{};
-  float* emb[4] = {};      // Pg, Qg, Pm, Qm
-  float* emb_m[4] = {};
-  float* emb_v[4] = {};
-  int64_t emb_rows[4] = {}, emb_cols[4] = {};
-  float *F = nullptr, *Fm = nullptr, *Fv = nullptr;  // flat tower + predict block (current copy)
-  float* WT = nullptr;                                // its transposed tower weights (current copy)
-  float *Fo = nullptr, *WTo = nullptr;                // the other copies (the next step's)
-  int wt_n = 0;                                       // floats of the W^T block
+  Acts A{};
+  float *F = nullptr, *WT = nullptr;    // the current copy of flat / wt
+  float *Fo = nullptr, *WTo = nullptr;  // the other copies (the next step's)
+  int wt_n = 0;                         // floats of the W^T block
   int64_t max_blocks = 0;
-  Acts A{};                                           // training activations, max_blocks * 16 rows
-  float* acts = nullptr;
-  NcfJob* d_jobs = nullptr;
   int njobs = 0;
-  // training data
-  int64_t npos = 0;
-  int32_t *d_pos_u = nullptr, *d_pos_i = nullptr, *d_indices = nullptr;
-  int64_t* d_indptr = nullptr;
   uint32_t feistel_a = 1, feistel_c = 1;  // permute's domain Z_a x Z_c (feistel_dims)
   uint32_t k0 = 0, k1 = 0;
-  // sample chunk
-  int32_t *d_u = nullptr, *d_i = nullptr;
-  float* d_y = nullptr;
-  int64_t chunk_cap = 0;
-  double* d_loss = nullptr;
-  int32_t* d_err = nullptr;
-  int32_t t = 0;  // Adam steps taken
-  int32_t *cur_u = nullptr, *cur_i = nullptr;  // step each row's p, m, v are current at (-1: never touched)
-  int32_t flushed = 0;                         // every row is current at this step
-  struct {                                     // step t's row Adam, run with step t + 1's catch-up
+  int32_t t = 0;        // Adam steps taken
+  int32_t flushed = 0;  // every row is current at this step
+  struct {              // step t's row Adam, run with step t + 1's catch-up
     const int32_t *u = nullptr, *i = nullptr;
     int n = 0;
     AdamArgs a{};
   } pend;
-  float2 *d_step = nullptr, *d_pw = nullptr;   // catch-up tables (CatchArgs)
-  int32_t nstep = 0;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
   bool prof_on = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> prof[4];
   std::vector<hipEvent_t> pool;
 };
 
-static int ncf_dev(ncf_handle* h) {
-  HIPCHK(hipSetDevice(h->cfg.device));
-  return 0;
-}
+// rows and columns of embedding table tb (Pg, Qg, Pm, Qm)
+static int64_t emb_rows(const Dims& D, int tb) { return tb & 1 ? D.I : D.U; }
+static int emb_cols(const Dims& D, int tb) { return tb < 2 ? D.d : D.E; }
 
 static hipEvent_t ncf_event(ncf_handle* h) {
   hipEvent_t e = nullptr;
@@ -96,13 +100,13 @@ struct NcfProf {  // event pair around a launch while profiling
   int kind;
   hipEvent_t a = nullptr;
   NcfProf(ncf_handle* hh, int k) : h(hh), kind(k) {
-    if (h->prof_on && (a = ncf_event(h))) (void)hipEventRecord(a, h->stream);
+    if (h->prof_on && (a = ncf_event(h))) (void)hipEventRecord(a, h->lane.stream);
   }
   ~NcfProf() {
     if (!a) return;
     hipEvent_t b = ncf_event(h);
     if (!b) return;
-    (void)hipEventRecord(b, h->stream);
+    (void)hipEventRecord(b, h->lane.stream);
     h->prof[kind].push_back({a, b});
   }
 };
@@ -116,8 +120,8 @@ static bool param_at(ncf_handle* h, int idx, float** p, int64_t* rows, int64_t* 
   const Dims& D = h->D;
   if (idx < 4) {
     *p = h->emb[idx];
-    *rows = h->emb_rows[idx];
-    *cols = h->emb_cols[idx];
+    *rows = emb_rows(D, idx);
+    *cols = emb_cols(D, idx);
     return true;
   }
   idx -= 4;
@@ -161,11 +165,11 @@ static RowSides row_sides(const ncf_handle* h, const int32_t* u, const int32_t* 
       S.W[k] = h->emb[tb];
       S.M[k] = h->emb_m[tb];
       S.V[k] = h->emb_v[tb];
-      S.G[k] = tb == 0 ? h->G.Pg : tb == 1 ? h->G.Qg : tb == 2 ? h->G.Pm : h->G.Qm;
-      S.cols[k] = (int)h->emb_cols[tb];
+      S.G[k] = h->grad[tb];
+      S.cols[k] = emb_cols(h->D, tb);
     }
-    S.cur = side ? h->cur_i : h->cur_u;
-    S.touch = side ? h->G.touch_i : h->G.touch_u;
+    S.cur = h->cur[side];
+    S.touch = h->touch[side];
     S.rows = side ? h->D.I : h->D.U;
   }
   R.ids[0] = u;
@@ -179,7 +183,7 @@ static CatchArgs catch_args(const ncf_handle* h, int32_t target) {
   CatchArgs c;
   c.step = h->d_step;
   c.pw = h->d_pw;
-  c.nstep = h->nstep;
+  c.nstep = (int32_t)h->d_step.size();
   c.lr = h->cfg.lr;
   c.eps = h->cfg.eps;
   c.log2_b1 = (float)std::log2((double)h->cfg.beta1);
@@ -188,33 +192,12 @@ static CatchArgs catch_args(const ncf_handle* h, int32_t target) {
   return c;
 }
 
-// the catch-up's tables, in double as the step's own AdamArgs: torch's step_size(s) and
-// 1 / bc2_sqrt(s) for every step whose bias corrections f32 tells from 1 (then lr and 1), and
-// b1^j, b2^(j/2) for the terms
-static int catch_tables(ncf_handle* h) {
-  const double b1 = h->cfg.beta1, b2 = h->cfg.beta2, lr = h->cfg.lr;
-  int64_t n = 1;
-  while (n < (1 << 22) && (std::pow(b1, (double)n) > 0x1p-26 || std::pow(b2, (double)n) > 0x1p-26)) n *= 2;
-  std::vector<float2> st((size_t)n), pw(kCatchTerms);
-  for (int64_t s = 1; s <= n; ++s)
-    st[s - 1] = make_float2((float)(lr / (1.0 - std::pow(b1, (double)s))),
-                            (float)(1.0 / std::sqrt(1.0 - std::pow(b2, (double)s))));
-  for (int j = 1; j <= kCatchTerms; ++j)
-    pw[j - 1] = make_float2((float)std::pow(b1, (double)j), (float)std::pow(b2, 0.5 * j));
-  if (int r = dalloc(&h->d_step, n)) return r;
-  if (int r = dalloc(&h->d_pw, kCatchTerms)) return r;
-  HIPCHK(hipMemcpy(h->d_step, st.data(), sizeof(float2) * n, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(h->d_pw, pw.data(), sizeof(float2) * kCatchTerms, hipMemcpyHostToDevice));
-  h->nstep = (int32_t)n;
-  return 0;
-}
-
 // the last step's row Adam, when it is still pending (before anything reads the rows or the
 // sample buffers it points into are refilled)
 static int flush_pending(ncf_handle* h) {
   if (!h->pend.n) return 0;
   NcfProf ps(h, 2);
-  HIPCHK(adam_rows(row_sides(h, h->pend.u, h->pend.i), h->pend.n, h->t, h->pend.a, h->stream));
+  HIPCHK(adam_rows(row_sides(h, h->pend.u, h->pend.i), h->pend.n, h->t, h->pend.a, h->lane.stream));
   h->pend.n = 0;
   return 0;
 }
@@ -225,7 +208,7 @@ static int ncf_flush(ncf_handle* h) {
   if (h->flushed == h->t) return 0;
   {
     NcfProf ps(h, 3);
-    HIPCHK(catch_up(row_sides(h, nullptr, nullptr), 0, catch_args(h, h->t), h->stream));
+    HIPCHK(catch_up(row_sides(h, nullptr, nullptr), 0, catch_args(h, h->t), h->lane.stream));
   }
   h->flushed = h->t;
   return 0;
@@ -247,9 +230,9 @@ static void point_params(ncf_handle* h) {
 
 // W^T from W in the current copy, then the other copy made equal (after init / set_param)
 static int sync_copies(ncf_handle* h) {
-  HIPCHK(transpose(h->D, h->P, h->stream));
-  HIPCHK(hipMemcpyAsync(h->Fo, h->F, 4 * (size_t)h->D.flat_n, hipMemcpyDeviceToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->WTo, h->WT, 4 * (size_t)h->wt_n, hipMemcpyDeviceToDevice, h->stream));
+  HIPCHK(transpose(h->D, h->P, h->lane.stream));
+  HIPCHK(hipMemcpyAsync(h->Fo, h->F, 4 * (size_t)h->D.flat_n, hipMemcpyDeviceToDevice, h->lane.stream));
+  HIPCHK(hipMemcpyAsync(h->WTo, h->WT, 4 * (size_t)h->wt_n, hipMemcpyDeviceToDevice, h->lane.stream));
   return 0;
 }
 
@@ -323,11 +306,11 @@ static std::vector<NcfJob> make_jobs(const ncf_handle* h) {
 
 static SamplerArgs ncf_sampler(ncf_handle* h) {
   SamplerArgs a{};
-  a.pos_u = h->d_pos_u;
-  a.pos_i = h->d_pos_i;
-  a.indptr = h->d_indptr;
-  a.indices = h->d_indices;
-  a.npos = h->npos;
+  a.pos_u = h->train.pos_u;
+  a.pos_i = h->train.pos_i;
+  a.indptr = h->train.indptr;
+  a.indices = h->train.indices;
+  a.npos = h->train.n;
   a.item_num = h->cfg.item_num;
   a.num_ng = h->cfg.num_ng;
   a.world = 1;
@@ -340,10 +323,10 @@ static SamplerArgs ncf_sampler(ncf_handle* h) {
 
 static int ncf_check_err(ncf_handle* h) {
   int32_t e = 0;
-  HIPCHK(hipMemcpyAsync(&e, h->d_err, 4, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
+  HIPCHK(hipMemcpyAsync(&e, h->d_err, 4, hipMemcpyDeviceToHost, h->lane.stream));
+  HIPCHK(hipStreamSynchronize(h->lane.stream));
   if (e) {
-    HIPCHK(hipMemsetAsync(h->d_err, 0, 4, h->stream));
+    HIPCHK(hipMemsetAsync(h->d_err, 0, 4, h->lane.stream));
     if (e & 2) return fail(BPRMF_E_NO_NEGATIVE, "a user has every item as a positive: no negative to sample");
     return fail(BPRMF_E_RANGE, "user/item id out of range (device check)");
   }
@@ -360,7 +343,7 @@ static int ncf_step(ncf_handle* h, const int32_t* u, const int32_t* i, const flo
   {  // step t - 1's row Adam (pending) and this step's catch-up to t - 1
     NcfProf ps(h, 3);
     HIPCHK(rows(row_sides(h, h->pend.u, h->pend.i), h->pend.n, h->pend.a, R, n, catch_args(h, t - 1),
-                h->stream));
+                h->lane.stream));
     h->pend.n = 0;
   }
   const double b1 = h->cfg.beta1, b2 = h->cfg.beta2;
@@ -376,9 +359,9 @@ static int ncf_step(ncf_handle* h, const int32_t* u, const int32_t* i, const flo
     const RowSides Rn = row_sides(h, nu, ni);
     const CatchArgs cn = catch_args(h, t);
     HIPCHK(fwdbwd(h->D, h->P, h->G, h->A, u, i, y, n, t, h->d_loss, h->d_err, nu ? &Rn : nullptr, nu ? nn : 0,
-                  &cn, h->stream));
+                  &cn, h->lane.stream));
     HIPCHK(back(h->D, h->P, h->G, h->d_jobs, h->njobs, u, i, n, h->F, h->Fo, h->WTo, h->Fm, h->Fv, a,
-                h->stream));
+                h->lane.stream));
   }
   std::swap(h->F, h->Fo);  // the updated tower / predict weights are the current copy
   std::swap(h->WT, h->WTo);
@@ -391,46 +374,136 @@ static int ncf_step(ncf_handle* h, const int32_t* u, const int32_t* i, const flo
 }
 
 static int ncf_begin(ncf_handle* h) {
-  if (int r = ncf_dev(h)) return r;
+  if (int r = h->lane.use()) return r;
   if (int r = flush_pending(h)) return r;
-  HIPCHK(hipMemsetAsync(h->d_loss, 0, sizeof(double) * kLossSlotsNcf, h->stream));
-  HIPCHK(hipEventRecord(h->ev0, h->stream));
-  return 0;
+  HIPCHK(hipMemsetAsync(h->d_loss, 0, sizeof(double) * kLossSlotsNcf, h->lane.stream));
+  return h->lane.begin();
 }
 
 static int ncf_end(ncf_handle* h, bprmf_stats* st, int64_t samples, int64_t steps) {
   if (int r = flush_pending(h)) return r;
-  HIPCHK(hipEventRecord(h->ev1, h->stream));
+  double seconds = 0.0;
+  if (int r = h->lane.end(&seconds)) return r;
   std::vector<double> slots(kLossSlotsNcf);
   HIPCHK(hipMemcpyAsync(slots.data(), h->d_loss, sizeof(double) * kLossSlotsNcf, hipMemcpyDeviceToHost,
-                        h->stream));
-  HIPCHK(hipEventSynchronize(h->ev1));
-  float ms = 0;
-  HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-  if (int r = ncf_check_err(h)) return r;
+                        h->lane.stream));
+  if (int r = ncf_check_err(h)) return r;  // waits for the stream
   if (st) {
     double l = 0;
     for (double v : slots) l += v;
     st->triplets = samples;
     st->steps = steps;
     st->loss = l;  // sum over the call's steps of each step's mean loss
-    st->seconds = ms * 1e-3;
+    st->seconds = seconds;
   }
   return 0;
 }
 
+// the sample chunk holds at least n samples; its contents are dropped when it grows
 static int ensure_chunk(ncf_handle* h, int64_t n) {
-  if (n <= h->chunk_cap) return 0;
-  void* ptrs[] = {h->d_u, h->d_i, h->d_y};
-  for (void* p : ptrs)
-    if (p) HIPCHK(hipFree(p));
-  h->d_u = h->d_i = nullptr;
-  h->d_y = nullptr;
-  h->chunk_cap = 0;
-  if (int r = dalloc(&h->d_u, n)) return r;
-  if (int r = dalloc(&h->d_i, n)) return r;
-  if (int r = dalloc(&h->d_y, n)) return r;
-  h->chunk_cap = n;
+  if (n <= h->d_y.size()) return 0;
+  if (int r = flush_pending(h)) return r;  // it points into the buffers freed here
+  h->d_y.reset();                          // no capacity while the three regrow
+  if (int r = h->d_u.alloc(n)) return r;
+  if (int r = h->d_i.alloc(n)) return r;
+  return h->d_y.alloc(n);
+}
+
+// the model's shapes and the layout of its flat tower + predict block
+static Dims make_dims(const ncf_config& c) {
+  Dims D{};
+  D.d = c.factor_num;
+  D.L = c.num_layers;
+  D.E = D.d << (D.L - 1);
+  D.model = c.model;
+  D.pred = D.model == kNeuMF ? 2 * D.d : D.d;
+  D.U = c.user_num;
+  D.I = c.item_num;
+  int off = 0;
+  for (int l = 0; l < D.L; ++l) {
+    D.nin[l] = D.d << (D.L - l);
+    D.nout[l] = D.nin[l] / 2;
+    D.off_W[l] = off;
+    off += D.nin[l] * D.nout[l];
+    D.off_b[l] = off;
+    off += D.nout[l];
+  }
+  D.off_wp = off;
+  off += D.pred;
+  D.off_bp = off;
+  off += 1;
+  D.flat_n = (off + 3) & ~3;
+  return D;
+}
+
+// every buffer of a new handle, zeroed or stamped, and the views into them
+static int alloc_buffers(ncf_handle* h) {
+  const Dims& D = h->D;
+  hipStream_t s = h->lane.stream;
+  for (int tb = 0; tb < 4; ++tb) {
+    const int64_t n = emb_rows(D, tb) * emb_cols(D, tb);
+    if (int r = h->emb[tb].alloc(n)) return r;
+    if (int r = h->emb_m[tb].zalloc(n)) return r;
+    if (int r = h->emb_v[tb].zalloc(n)) return r;
+    if (int r = h->grad[tb].zalloc(n)) return r;
+  }
+  std::vector<float> step, pw;
+  auto pairs = [](DevBuf<float2>& d, const std::vector<float>& v) {  // interleaved pairs
+    return d.upload(reinterpret_cast<const float2*>(v.data()), (int64_t)v.size() / 2);
+  };
+  int rc = 0;
+  if ((rc = ncf_catch_tables(h->cfg.lr, h->cfg.beta1, h->cfg.beta2, kCatchTerms, &step, &pw)) ||
+      (rc = pairs(h->d_step, step)) || (rc = pairs(h->d_pw, pw)))
+    return rc;
+  for (int side = 0; side < 2; ++side) {
+    const int64_t n = side ? D.I : D.U;
+    if (int r = h->cur[side].alloc(n)) return r;
+    if (int r = h->touch[side].alloc(n)) return r;
+    HIPCHK(hipMemsetAsync(h->cur[side], 0xFF, 4 * n, s));  // -1: never touched
+    HIPCHK(hipMemsetAsync(h->touch[side], 0xFF, 4 * n, s));
+  }
+  int wt = 0;
+  for (int l = 0; l < D.L; ++l) wt += D.nin[l] * D.nout[l];
+  h->wt_n = std::max(wt, 1);
+  for (int c = 0; c < 2; ++c) {
+    if (int r = h->flat[c].alloc(D.flat_n)) return r;
+    if (int r = h->wt[c].alloc(h->wt_n)) return r;
+  }
+  if (int r = h->Fm.zalloc(D.flat_n)) return r;
+  if (int r = h->Fv.zalloc(D.flat_n)) return r;
+  const int64_t rows = h->max_blocks * kSamples;
+  if (int r = h->acts.alloc(carve_acts(D, rows, true, nullptr, nullptr))) return r;
+  carve_acts(D, rows, true, h->acts, &h->A);
+  HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(h->A.ones), 0x3F800000, rows, s));
+  const std::vector<NcfJob> jobs = make_jobs(h);
+  h->njobs = (int)jobs.size();
+  if (int r = h->d_jobs.upload(jobs)) return r;
+  if (int r = h->d_loss.alloc(kLossSlotsNcf)) return r;
+  if (int r = h->d_err.zalloc(1)) return r;
+  h->F = h->flat[0], h->Fo = h->flat[1];
+  h->WT = h->wt[0], h->WTo = h->wt[1];
+  h->P.Pg = h->emb[0], h->P.Qg = h->emb[1], h->P.Pm = h->emb[2], h->P.Qm = h->emb[3];
+  h->G.Pg = h->grad[0], h->G.Qg = h->grad[1], h->G.Pm = h->grad[2], h->G.Qm = h->grad[3];
+  h->G.touch_u = h->touch[0], h->G.touch_i = h->touch[1];
+  point_params(h);
+  return 0;
+}
+
+// NCF._init_weight_ (NCFRecommender.py:65-82): normal(0.01) embeddings, xavier_uniform tower,
+// kaiming_uniform(a=1, 'sigmoid') predictor, zero biases
+static int init_weights(ncf_handle* h) {
+  const Dims& D = h->D;
+  hipStream_t s = h->lane.stream;
+  for (int tb = 0; tb < 4; ++tb)
+    HIPCHK(init(h->emb[tb], emb_rows(D, tb) * emb_cols(D, tb), 0, h->cfg.init_std, h->k0, h->k1,
+                1u + tb, s));
+  HIPCHK(hipMemsetAsync(h->F, 0, 4 * (size_t)D.flat_n, s));
+  for (int l = 0; l < D.L; ++l)
+    HIPCHK(init(h->P.W[l], (int64_t)D.nin[l] * D.nout[l], 1,
+                (float)std::sqrt(6.0 / (D.nin[l] + D.nout[l])), h->k0, h->k1, 16u + l, s));
+  HIPCHK(init(h->P.wp, D.pred, 1, (float)std::sqrt(3.0 / D.pred), h->k0, h->k1, 32u, s));
+  if (int r = sync_copies(h)) return r;
+  HIPCHK(hipStreamSynchronize(s));
   return 0;
 }
 
@@ -451,154 +524,27 @@ int ncf_create(const ncf_config* cfg, ncf_handle** out) {
   if (!(cfg->lr >= 0.f) || !(cfg->eps > 0.f) || !(cfg->beta1 >= 0.f && cfg->beta1 < 1.f) ||
       !(cfg->beta2 >= 0.f && cfg->beta2 < 1.f))
     return fail(BPRMF_E_INVALID, "bad Adam hyper-parameters");
-  auto* h = new ncf_handle();
+  std::unique_ptr<ncf_handle, decltype(&ncf_destroy)> h(new ncf_handle(), ncf_destroy);
   h->cfg = *cfg;
-  Dims& D = h->D;
-  D.d = cfg->factor_num;
-  D.L = cfg->num_layers;
-  D.E = D.d << (D.L - 1);
-  D.model = cfg->model;
-  D.pred = D.model == kNeuMF ? 2 * D.d : D.d;
-  D.U = cfg->user_num;
-  D.I = cfg->item_num;
-  int off = 0;
-  for (int l = 0; l < D.L; ++l) {
-    D.nin[l] = D.d << (D.L - l);
-    D.nout[l] = D.nin[l] / 2;
-    D.off_W[l] = off;
-    off += D.nin[l] * D.nout[l];
-    D.off_b[l] = off;
-    off += D.nout[l];
-  }
-  D.off_wp = off;
-  off += D.pred;
-  D.off_bp = off;
-  off += 1;
-  D.flat_n = (off + 3) & ~3;
-  h->emb_rows[0] = h->emb_rows[2] = D.U;
-  h->emb_rows[1] = h->emb_rows[3] = D.I;
-  h->emb_cols[0] = h->emb_cols[1] = D.d;
-  h->emb_cols[2] = h->emb_cols[3] = D.E;
+  h->D = make_dims(*cfg);
   h->max_blocks = (cfg->batch_size + kSamples - 1) / kSamples;
-  const uint64_t seed = cfg->seed;
-  h->k0 = (uint32_t)seed;
-  h->k1 = (uint32_t)(seed >> 32);
-  int rc = 0;
-#define TRY(x)          \
-  do {                  \
-    if ((rc = (x))) {   \
-      ncf_destroy(h);   \
-      return rc;        \
-    }                   \
-  } while (0)
-  TRY(ncf_dev(h));
-  if (fwdbwd_lds_bytes(D) > 160 * 1024) {
-    ncf_destroy(h);
+  h->k0 = (uint32_t)cfg->seed;
+  h->k1 = (uint32_t)(cfg->seed >> 32);
+  if (int r = h->lane.open(cfg->device)) return r;
+  if (fwdbwd_lds_bytes(h->D) > 160 * 1024)
     return fail(BPRMF_E_UNSUPPORTED, "the tower of factor_num %d x %d layers needs %zu B of LDS (> 160 KB)",
-                D.d, D.L, fwdbwd_lds_bytes(D));
-  }
-  if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess ||
-      hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess) {
-    ncf_destroy(h);
-    return fail(BPRMF_E_HIP, "stream/event creation failed");
-  }
-  auto memz = [&](void* p, size_t bytes) -> int {
-    if (p && bytes) HIPCHK(hipMemsetAsync(p, 0, bytes, h->stream));
-    return 0;
-  };
-  for (int tb = 0; tb < 4; ++tb) {
-    const int64_t n = h->emb_rows[tb] * h->emb_cols[tb];
-    TRY(dalloc(&h->emb[tb], n));
-    TRY(dalloc(&h->emb_m[tb], n));
-    TRY(dalloc(&h->emb_v[tb], n));
-    TRY(memz(h->emb_m[tb], 4 * n));
-    TRY(memz(h->emb_v[tb], 4 * n));
-  }
-  TRY(dalloc(&h->G.Pg, D.U * D.d));
-  TRY(dalloc(&h->G.Qg, D.I * D.d));
-  TRY(dalloc(&h->G.Pm, D.U * D.E));
-  TRY(dalloc(&h->G.Qm, D.I * D.E));
-  TRY(memz(h->G.Pg, 4 * D.U * D.d));
-  TRY(memz(h->G.Qg, 4 * D.I * D.d));
-  TRY(memz(h->G.Pm, 4 * D.U * D.E));
-  TRY(memz(h->G.Qm, 4 * D.I * D.E));
-  TRY(catch_tables(h));
-  TRY(dalloc(&h->cur_u, D.U));
-  TRY(dalloc(&h->cur_i, D.I));
-  HIPCHK(hipMemsetAsync(h->cur_u, 0xFF, 4 * D.U, h->stream));  // -1: never touched
-  HIPCHK(hipMemsetAsync(h->cur_i, 0xFF, 4 * D.I, h->stream));
-  TRY(dalloc(&h->G.touch_u, D.U));
-  TRY(dalloc(&h->G.touch_i, D.I));
-  HIPCHK(hipMemsetAsync(h->G.touch_u, 0xFF, 4 * D.U, h->stream));
-  HIPCHK(hipMemsetAsync(h->G.touch_i, 0xFF, 4 * D.I, h->stream));
-  TRY(dalloc(&h->F, D.flat_n));
-  TRY(dalloc(&h->Fo, D.flat_n));
-  TRY(dalloc(&h->Fm, D.flat_n));
-  TRY(dalloc(&h->Fv, D.flat_n));
-  TRY(memz(h->Fm, 4 * D.flat_n));
-  TRY(memz(h->Fv, 4 * D.flat_n));
-  int wt = 0;
-  for (int l = 0; l < D.L; ++l) wt += D.nin[l] * D.nout[l];
-  h->wt_n = std::max(wt, 1);
-  TRY(dalloc(&h->WT, h->wt_n));
-  TRY(dalloc(&h->WTo, h->wt_n));
-  {
-    const int64_t rows = h->max_blocks * kSamples;
-    TRY(dalloc(&h->acts, carve_acts(D, rows, true, nullptr, nullptr)));
-    carve_acts(D, rows, true, h->acts, &h->A);
-    HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(h->A.ones), 0x3F800000, rows, h->stream));
-    const std::vector<NcfJob> jobs = make_jobs(h);
-    h->njobs = (int)jobs.size();
-    TRY(dalloc(&h->d_jobs, h->njobs));
-    HIPCHK(hipMemcpy(h->d_jobs, jobs.data(), sizeof(NcfJob) * jobs.size(), hipMemcpyHostToDevice));
-  }
-  TRY(dalloc(&h->d_loss, kLossSlotsNcf));
-  TRY(dalloc(&h->d_err, 1));
-  TRY(memz(h->d_err, 4));
-  h->P.Pg = h->emb[0];
-  h->P.Qg = h->emb[1];
-  h->P.Pm = h->emb[2];
-  h->P.Qm = h->emb[3];
-  point_params(h);
-  // NCF._init_weight_ (NCFRecommender.py:65-82): normal(0.01) embeddings, xavier_uniform tower,
-  // kaiming_uniform(a=1, 'sigmoid') predictor, zero biases
-  hipError_t e = hipSuccess;
-  for (int tb = 0; tb < 4 && e == hipSuccess; ++tb)
-    e = init(h->emb[tb], h->emb_rows[tb] * h->emb_cols[tb], 0, cfg->init_std, h->k0, h->k1, 1u + tb, h->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(h->F, 0, 4 * D.flat_n, h->stream);
-  for (int l = 0; l < D.L && e == hipSuccess; ++l)
-    e = init(h->P.W[l], (int64_t)D.nin[l] * D.nout[l], 1,
-             (float)std::sqrt(6.0 / (D.nin[l] + D.nout[l])), h->k0, h->k1, 16u + l, h->stream);
-  if (e == hipSuccess) e = init(h->P.wp, D.pred, 1, (float)std::sqrt(3.0 / D.pred), h->k0, h->k1, 32u, h->stream);
-  if (e == hipSuccess && sync_copies(h)) e = hipErrorUnknown;
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  if (e != hipSuccess) {
-    ncf_destroy(h);
-    return fail(BPRMF_E_HIP, "ncf init: %s", hipGetErrorString(e));
-  }
-#undef TRY
-  *out = h;
+                h->D.d, h->D.L, fwdbwd_lds_bytes(h->D));
+  if (int r = alloc_buffers(h.get())) return r;
+  if (int r = init_weights(h.get())) return r;
+  *out = h.release();
   return 0;
 }
 
 int ncf_destroy(ncf_handle* h) {
   if (!h) return 0;
-  (void)!hipSetDevice(h->cfg.device);
-  if (h->stream) (void)!hipStreamSynchronize(h->stream);
-  for (int tb = 0; tb < 4; ++tb) {
-    void* p[] = {h->emb[tb], h->emb_m[tb], h->emb_v[tb]};
-    for (void* x : p)
-      if (x) (void)!hipFree(x);
-  }
-  void* ptrs[] = {h->G.Pg, h->G.Qg, h->G.Pm, h->G.Qm, h->cur_u, h->cur_i, h->G.touch_u, h->G.touch_i, h->d_step, h->d_pw, h->F, h->Fm,
-                  h->Fv, h->WT, h->Fo, h->WTo, h->acts, h->d_jobs, h->d_pos_u, h->d_pos_i, h->d_indices, h->d_indptr,
-                  h->d_u, h->d_i, h->d_y, h->d_loss, h->d_err};
-  for (void* x : ptrs)
-    if (x) (void)!hipFree(x);
-  for (hipEvent_t e : h->pool) (void)!hipEventDestroy(e);
-  if (h->ev0) (void)!hipEventDestroy(h->ev0);
-  if (h->ev1) (void)!hipEventDestroy(h->ev1);
-  if (h->stream) (void)!hipStreamDestroy(h->stream);
+  (void)h->lane.use();
+  if (h->lane.stream) (void)hipStreamSynchronize(h->lane.stream);
+  for (hipEvent_t e : h->pool) (void)hipEventDestroy(e);
   delete h;
   return 0;
 }
@@ -621,13 +567,13 @@ int ncf_set_param(ncf_handle* h, int32_t index, const float* data) {
   float* p;
   int64_t r, c;
   if (!param_at(h, index, &p, &r, &c)) return fail(BPRMF_E_RANGE, "no parameter %d", index);
-  if (int rc = ncf_dev(h)) return rc;
+  if (int rc = h->lane.use()) return rc;
   if (index < 4)  // the moments of the rows keep counting from the current step
     if (int rc = ncf_flush(h)) return rc;
-  HIPCHK(hipStreamSynchronize(h->stream));
+  HIPCHK(hipStreamSynchronize(h->lane.stream));
   HIPCHK(hipMemcpy(p, data, 4 * r * c, hipMemcpyHostToDevice));
   if (int rc = sync_copies(h)) return rc;
-  HIPCHK(hipStreamSynchronize(h->stream));
+  HIPCHK(hipStreamSynchronize(h->lane.stream));
   return 0;
 }
 
@@ -636,57 +582,35 @@ int ncf_get_param(ncf_handle* h, int32_t index, float* data) {
   float* p;
   int64_t r, c;
   if (!param_at(h, index, &p, &r, &c)) return fail(BPRMF_E_RANGE, "no parameter %d", index);
-  if (int rc = ncf_dev(h)) return rc;
+  if (int rc = h->lane.use()) return rc;
   if (index < 4)
     if (int rc = ncf_flush(h)) return rc;
-  HIPCHK(hipStreamSynchronize(h->stream));
+  HIPCHK(hipStreamSynchronize(h->lane.stream));
   HIPCHK(hipMemcpy(data, p, 4 * r * c, hipMemcpyDeviceToHost));
   return 0;
 }
 
 int ncf_set_train(ncf_handle* h, const int32_t* users, const int32_t* items, int64_t nnz) {
   if (!h || nnz < 0 || (nnz > 0 && (!users || !items))) return fail(BPRMF_E_INVALID, "bad arguments");
-  if (int r = ncf_dev(h)) return r;
-  std::vector<uint64_t> keys((size_t)nnz);
-  for (int64_t k = 0; k < nnz; ++k) {
-    if (users[k] < 0 || users[k] >= h->cfg.user_num || items[k] < 0 || items[k] >= h->cfg.item_num)
-      return fail(BPRMF_E_RANGE, "positive %lld = (%d, %d) out of range", (long long)k, users[k], items[k]);
-    keys[k] = ((uint64_t)users[k] << 32) | (uint32_t)items[k];
-  }
-  std::sort(keys.begin(), keys.end());
-  keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
-  std::vector<int64_t> indptr(h->cfg.user_num + 1, 0);
-  std::vector<int32_t> indices(keys.size());
-  for (size_t k = 0; k < keys.size(); ++k) {
-    indptr[(keys[k] >> 32) + 1]++;
-    indices[k] = (int32_t)(keys[k] & 0xFFFFFFFFu);
-  }
-  for (int64_t u = 0; u < h->cfg.user_num; ++u) indptr[u + 1] += indptr[u];
-  void* olds[] = {h->d_pos_u, h->d_pos_i, h->d_indptr, h->d_indices};
-  for (void* p : olds)
-    if (p) HIPCHK(hipFree(p));
-  h->d_pos_u = h->d_pos_i = h->d_indices = nullptr;
-  h->d_indptr = nullptr;
-  if (int r = dalloc(&h->d_pos_u, nnz)) return r;
-  if (int r = dalloc(&h->d_pos_i, nnz)) return r;
-  if (int r = dalloc(&h->d_indptr, h->cfg.user_num + 1)) return r;
-  if (int r = dalloc(&h->d_indices, (int64_t)indices.size())) return r;
-  if (nnz) {
-    HIPCHK(hipMemcpy(h->d_pos_u, users, 4 * nnz, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(h->d_pos_i, items, 4 * nnz, hipMemcpyHostToDevice));
-  }
-  HIPCHK(hipMemcpy(h->d_indptr, indptr.data(), 8 * indptr.size(), hipMemcpyHostToDevice));
-  if (!indices.empty())
-    HIPCHK(hipMemcpy(h->d_indices, indices.data(), 4 * indices.size(), hipMemcpyHostToDevice));
-  h->npos = nnz;
-  const uint64_t N = (uint64_t)nnz * (uint64_t)(1 + h->cfg.num_ng);
-  feistel_dims(N, &h->feistel_a, &h->feistel_c);
+  if (int r = h->lane.use()) return r;
+  const int64_t U = h->cfg.user_num;
+  ShardCsr csr;  // world 1: every positive in input order, the CSR over all users
+  if (int r = build_shard_csr(users, items, nnz, nullptr, nullptr, 0, U, h->cfg.item_num, 1, 0, U, &csr))
+    return r;
+  TrainSet t;  // built beside the handle's, which it replaces only when whole
+  int rc = 0;
+  if ((rc = t.pos_u.upload(csr.pos_u)) || (rc = t.pos_i.upload(csr.pos_i)) ||
+      (rc = t.indptr.upload(csr.indptr)) || (rc = t.indices.upload(csr.indices)))
+    return rc;
+  t.n = nnz;
+  h->train = std::move(t);
+  feistel_dims((uint64_t)nnz * (uint64_t)(1 + h->cfg.num_ng), &h->feistel_a, &h->feistel_c);
   return 0;
 }
 
 int ncf_epoch_size(ncf_handle* h, int64_t* samples, int64_t* steps) {
   if (!h) return fail(BPRMF_E_INVALID, "null handle");
-  const int64_t N = h->npos * (1 + h->cfg.num_ng);
+  const int64_t N = h->train.n * (1 + h->cfg.num_ng);
   if (samples) *samples = N;
   if (steps) *steps = (N + h->cfg.batch_size - 1) / h->cfg.batch_size;
   return 0;
@@ -706,9 +630,9 @@ int ncf_train_samples(ncf_handle* h, const int32_t* u, const int32_t* i, const f
   for (int64_t off = 0; off < n; off += chunk) {
     const int64_t m = std::min(chunk, n - off);
     if (int r = flush_pending(h)) return r;  // it points into the buffers refilled here
-    HIPCHK(hipMemcpyAsync(h->d_u, u + off, 4 * m, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->d_i, i + off, 4 * m, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->d_y, y + off, 4 * m, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->d_u, u + off, 4 * m, hipMemcpyHostToDevice, h->lane.stream));
+    HIPCHK(hipMemcpyAsync(h->d_i, i + off, 4 * m, hipMemcpyHostToDevice, h->lane.stream));
+    HIPCHK(hipMemcpyAsync(h->d_y, y + off, 4 * m, hipMemcpyHostToDevice, h->lane.stream));
     for (int64_t s = 0; s < m; s += B, ++steps) {
       const int64_t s2 = s + B;  // the next step's samples, when they are in this chunk
       if (int r = ncf_step(h, h->d_u + s, h->d_i + s, h->d_y + s, (int)std::min(B, m - s),
@@ -716,14 +640,14 @@ int ncf_train_samples(ncf_handle* h, const int32_t* u, const int32_t* i, const f
                            (int)std::min(B, std::max<int64_t>(0, m - s2))))
         return r;
     }
-    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipStreamSynchronize(h->lane.stream));
   }
   return ncf_end(h, st, n, steps);
 }
 
 int ncf_train_steps(ncf_handle* h, uint32_t epoch, int64_t first_step, int64_t n_steps, bprmf_stats* st) {
   if (!h || first_step < 0 || n_steps < 0) return fail(BPRMF_E_INVALID, "bad arguments");
-  if (!h->d_pos_u || h->npos == 0) return fail(BPRMF_E_STATE, "call ncf_set_train first");
+  if (!h->train.pos_u.size()) return fail(BPRMF_E_STATE, "call ncf_set_train first");
   int64_t N, S;
   ncf_epoch_size(h, &N, &S);
   if (first_step + n_steps > S) return fail(BPRMF_E_INVALID, "steps beyond the epoch's %lld", (long long)S);
@@ -738,7 +662,8 @@ int ncf_train_steps(ncf_handle* h, uint32_t epoch, int64_t first_step, int64_t n
     if (int r = flush_pending(h)) return r;  // it points into the buffers refilled here
     {
       NcfProf ps(h, 0);
-      HIPCHK(ncf::sample(ncf_sampler(h), epoch, off, m, h->d_u, h->d_i, h->d_y, h->d_err, h->stream));
+      HIPCHK(ncf::sample(ncf_sampler(h), epoch, off, m, h->d_u, h->d_i, h->d_y, h->d_err,
+                         h->lane.stream));
     }
     for (int64_t s = 0; s < m; s += B, ++steps) {
       const int64_t s2 = s + B;  // the next step's samples, when they are in this chunk
@@ -760,17 +685,17 @@ int ncf_train_epoch(ncf_handle* h, uint32_t epoch, bprmf_stats* st) {
 
 int ncf_sample(ncf_handle* h, uint32_t epoch, int64_t first, int64_t n, int32_t* u, int32_t* i, float* y) {
   if (!h || n < 0 || first < 0 || (n > 0 && (!u || !i || !y))) return fail(BPRMF_E_INVALID, "bad arguments");
-  if (!h->d_pos_u || h->npos == 0) return fail(BPRMF_E_STATE, "call ncf_set_train first");
+  if (!h->train.pos_u.size()) return fail(BPRMF_E_STATE, "call ncf_set_train first");
   int64_t N;
   ncf_epoch_size(h, &N, nullptr);
   if (first + n > N) return fail(BPRMF_E_INVALID, "samples outside the epoch");
-  if (int r = ncf_dev(h)) return r;
+  if (int r = h->lane.use()) return r;
   if (n == 0) return 0;
   if (int r = ensure_chunk(h, n)) return r;
-  HIPCHK(ncf::sample(ncf_sampler(h), epoch, first, n, h->d_u, h->d_i, h->d_y, h->d_err, h->stream));
-  HIPCHK(hipMemcpyAsync(u, h->d_u, 4 * n, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipMemcpyAsync(i, h->d_i, 4 * n, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipMemcpyAsync(y, h->d_y, 4 * n, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(ncf::sample(ncf_sampler(h), epoch, first, n, h->d_u, h->d_i, h->d_y, h->d_err, h->lane.stream));
+  HIPCHK(hipMemcpyAsync(u, h->d_u, 4 * n, hipMemcpyDeviceToHost, h->lane.stream));
+  HIPCHK(hipMemcpyAsync(i, h->d_i, 4 * n, hipMemcpyDeviceToHost, h->lane.stream));
+  HIPCHK(hipMemcpyAsync(y, h->d_y, 4 * n, hipMemcpyDeviceToHost, h->lane.stream));
   return ncf_check_err(h);
 }
 
@@ -781,7 +706,7 @@ int ncf_predict(ncf_handle* h, const int32_t* u, const int32_t* i, int64_t n, fl
     if (i[k] < 0 || i[k] >= h->cfg.item_num) return fail(BPRMF_E_RANGE, "Invalid item code");
   }
   if (n == 0) return 0;
-  if (int r = ncf_dev(h)) return r;
+  if (int r = h->lane.use()) return r;
   if (int r = flush_pending(h)) return r;
   // the rows read are brought to the current step: the requested ones, or every row for a long request
   const bool whole = 2 * n >= h->D.U + h->D.I;
@@ -790,36 +715,33 @@ int ncf_predict(ncf_handle* h, const int32_t* u, const int32_t* i, int64_t n, fl
   // ids, logits and the forward's activations for chunks of up to 64k samples
   const int64_t chunk = std::min<int64_t>((n + kSamples - 1) / kSamples * kSamples, 1 << 16);
   const int64_t act_n = carve_acts(h->D, chunk, false, nullptr, nullptr);
-  int32_t* buf = nullptr;
+  DevBuf<int32_t> buf;
   const int64_t act_off = (3 * n + 15) & ~(int64_t)15;  // float4-aligned activations
-  if (int r = dalloc(&buf, act_off + act_n)) return r;
+  if (int r = buf.alloc(act_off + act_n)) return r;
   float* z = reinterpret_cast<float*>(buf + 2 * n);
   Acts A;
   carve_acts(h->D, chunk, false, reinterpret_cast<float*>(buf + act_off), &A);
-  int rc = 0;
-  hipError_t e = hipMemcpyAsync(buf, u, 4 * n, hipMemcpyHostToDevice, h->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(buf + n, i, 4 * n, hipMemcpyHostToDevice, h->stream);
-  if (e == hipSuccess && !whole && h->flushed != h->t)
-    e = catch_up(row_sides(h, buf, buf + n), n, catch_args(h, h->t), h->stream);
-  for (int64_t off = 0; off < n && e == hipSuccess; off += chunk)
-    e = forward(h->D, h->P, A, buf + off, buf + n + off, (int)std::min(n - off, chunk), z + off, h->d_err,
-                h->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(out, z, 4 * n, hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  if (e != hipSuccess) rc = fail(BPRMF_E_HIP, "ncf_predict: %s", hipGetErrorString(e));
-  (void)!hipFree(buf);
-  if (rc) return rc;
+  hipStream_t s = h->lane.stream;
+  HIPCHK(hipMemcpyAsync(buf, u, 4 * n, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(buf + n, i, 4 * n, hipMemcpyHostToDevice, s));
+  if (!whole && h->flushed != h->t)
+    HIPCHK(catch_up(row_sides(h, buf, buf + n), n, catch_args(h, h->t), s));
+  for (int64_t off = 0; off < n; off += chunk)
+    HIPCHK(forward(h->D, h->P, A, buf + off, buf + n + off, (int)std::min(n - off, chunk), z + off,
+                   h->d_err, s));
+  HIPCHK(hipMemcpyAsync(out, z, 4 * n, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
   return ncf_check_err(h);
 }
 
 int ncf_active_rows(ncf_handle* h, int64_t* users, int64_t* items) {
   if (!h || !users || !items) return fail(BPRMF_E_INVALID, "null argument");
-  if (int r = ncf_dev(h)) return r;
+  if (int r = h->lane.use()) return r;
   if (int r = flush_pending(h)) return r;
-  HIPCHK(hipStreamSynchronize(h->stream));
+  HIPCHK(hipStreamSynchronize(h->lane.stream));
   std::vector<int32_t> tu(h->D.U), ti(h->D.I);
-  HIPCHK(hipMemcpy(tu.data(), h->cur_u, 4 * h->D.U, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(ti.data(), h->cur_i, 4 * h->D.I, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(tu.data(), h->cur[0], 4 * h->D.U, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(ti.data(), h->cur[1], 4 * h->D.I, hipMemcpyDeviceToHost));
   *users = std::count_if(tu.begin(), tu.end(), [](int32_t x) { return x >= 0; });
   *items = std::count_if(ti.begin(), ti.end(), [](int32_t x) { return x >= 0; });
   return 0;
@@ -827,8 +749,8 @@ int ncf_active_rows(ncf_handle* h, int64_t* users, int64_t* items) {
 
 int ncf_profile(ncf_handle* h, int32_t enable) {
   if (!h) return fail(BPRMF_E_INVALID, "null handle");
-  if (int r = ncf_dev(h)) return r;
-  HIPCHK(hipStreamSynchronize(h->stream));
+  if (int r = h->lane.use()) return r;
+  HIPCHK(hipStreamSynchronize(h->lane.stream));
   h->prof_on = enable != 0;
   for (auto& v : h->prof) v.clear();
   for (hipEvent_t e : h->pool) (void)!hipEventDestroy(e);
@@ -838,8 +760,8 @@ int ncf_profile(ncf_handle* h, int32_t enable) {
 
 int ncf_profile_read(ncf_handle* h, bprmf_kprof* out) {
   if (!h || !out) return fail(BPRMF_E_INVALID, "null argument");
-  if (int r = ncf_dev(h)) return r;
-  HIPCHK(hipStreamSynchronize(h->stream));
+  if (int r = h->lane.use()) return r;
+  HIPCHK(hipStreamSynchronize(h->lane.stream));
   memset(out, 0, sizeof *out);
   for (int k = 0; k < 4; ++k) {
     double tot = 0;

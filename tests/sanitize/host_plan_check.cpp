@@ -1,9 +1,9 @@
 // host_plan_check.cpp — drives the host-only planning logic of libbprmf_amd (csrc/host_plan.cpp:
 // the shard's positive lists behind bprmf_set_train_ex, the sharded runner's geometry, exchange
 // capacity and apply-plan sizes, the IPC blobs' device comparison; csrc/model_plan.cpp: the
-// rating-SGD levels, SVD++ lists, WRMF's CSR sides and launch plans, Item2Vec's noise CDF) under
-// AddressSanitizer +
-// UndefinedBehaviorSanitizer (tests/sanitize/Makefile; run by tests/test_sanitizers.py).
+// rating-SGD levels, SVD++ lists, WRMF's CSR sides and launch plans, Item2Vec's noise CDF, NCF's
+// catch-up tables) under AddressSanitizer + UndefinedBehaviorSanitizer (tests/sanitize/Makefile;
+// run by tests/test_sanitizers.py).
 // Every result is checked against a direct restatement; any sanitizer report aborts the run.
 #include <stdio.h>
 #include <stdlib.h>
@@ -317,6 +317,30 @@ static void check_cdf(std::mt19937_64& g, int64_t V) {
   CHECK(c[V - 1] == 2.0f);
 }
 
+// NCF's catch-up tables (ncf_catch_tables): the length and every entry from the formulas
+static void check_catch(double lr, double b1, double b2, int terms) {
+  std::vector<float> st, pw;
+  CHECK(ncf_catch_tables(lr, b1, b2, terms, &st, &pw) == 0);
+  const int64_t n = (int64_t)st.size() / 2, cap = 1 << 22;
+  CHECK(st.size() % 2 == 0 && n >= 1 && n <= cap && (n & (n - 1)) == 0);
+  // f32 cannot tell either bias correction from 1 once b^m <= 2^-26
+  auto settled = [&](int64_t m) { return std::pow(b1, (double)m) <= 0x1p-26 && std::pow(b2, (double)m) <= 0x1p-26; };
+  bool smallest = n == cap || settled(n);
+  for (int64_t m = 1; m < n; m *= 2) smallest = smallest && !settled(m);
+  CHECK(smallest);
+  bool steps = true, powers = true;
+  for (int64_t s = 1; s <= n && steps; ++s)
+    steps = st[2 * (s - 1)] == (float)(lr / (1.0 - std::pow(b1, (double)s))) &&
+            st[2 * (s - 1) + 1] == (float)(1.0 / std::sqrt(1.0 - std::pow(b2, (double)s)));
+  CHECK(steps);
+  CHECK((int64_t)pw.size() == 2 * (int64_t)terms);
+  if ((int64_t)pw.size() != 2 * (int64_t)terms) return;
+  for (int j = 1; j <= terms; ++j)
+    powers = powers && pw[2 * (j - 1)] == (float)std::pow(b1, (double)j) &&
+             pw[2 * (j - 1) + 1] == (float)std::pow(b2, 0.5 * j);
+  CHECK(powers);
+}
+
 int main() {
   std::mt19937_64 g(20261017);
   // the sibling models' plans (model_plan.cpp): empty input, one user, one item, every row on one
@@ -383,6 +407,19 @@ int main() {
     CHECK(sgns_noise_cdf(nan_, 3, &c) == BPRMF_E_INVALID && c.empty());
     CHECK(sgns_noise_cdf(zero, 3, &c) == BPRMF_E_INVALID && c.empty());
   }
+  // torch's default betas, no momentum at all, either one alone, and a beta2 whose bias correction
+  // outlasts the cap of 2^22 steps (f32 values, as the ABI carries them)
+  check_catch(1e-3f, 0.9f, 0.999f, 192);
+  check_catch(1e-3f, 0.0, 0.0, 192);
+  check_catch(0.5, 0.5f, 0.0, 5);
+  check_catch(1e-3f, 0.0, 0.999f, 0);
+  check_catch(1e-3f, 0.9f, 0.999999f, 192);
+  {
+    std::vector<float> st(2, 1.f), pw(2, 1.f);
+    CHECK(ncf_catch_tables(1e-3, 1.0, 0.5, 4, &st, &pw) == BPRMF_E_INVALID && st.empty() && pw.empty());
+    CHECK(ncf_catch_tables(1e-3, 0.5, -0.1, 4, &st, &pw) == BPRMF_E_INVALID && st.empty() && pw.empty());
+    CHECK(ncf_catch_tables(1e-3, 0.5, 0.5, -1, &st, &pw) == BPRMF_E_INVALID && st.empty() && pw.empty());
+  }
   // the sampler's search trees: empty users, one node, 2-4 levels (up to 16^3 + positives)
   check_tree(g, 50, 40, 16);
   check_tree(g, 200, 3000, 300);
@@ -390,6 +427,7 @@ int main() {
   // shard CSR: empty input, small and skewed shapes, every world size up to one node's 16 ranks
   check_csr(g, 1, 1, 0, 0, 1);
   check_csr(g, 5, 3, 0, 4, 2);
+  check_csr(g, 40, 48, 200, 0, 1);  // ncf_set_train's shape: one rank, no exclusions, duplicates
   for (int W : {1, 2, 3, 4, 7, 8, 16})
     for (int rep = 0; rep < 3; ++rep)
       check_csr(g, 1 + (int64_t)(g() % 300), 1 + (int64_t)(g() % 200), (int64_t)(g() % 5000),

@@ -175,3 +175,115 @@ def test_training_reduces_loss_and_ranks(rl, golden):
     zp = m.predict_logits(pos[:2000, 0], pos[:2000, 1])
     zn = m.predict_logits(pos[:2000, 0], g.integers(0, I, 2000))
     assert (zp > zn).mean() > 0.75
+
+
+# -- the handle's buffers and failure paths (csrc/ncf_capi.cpp): a tiny model, two train sets ----
+TU, TI = 40, 48
+
+
+def _tiny(rl, L=1, **kw):
+    return rl.NCF(TU, TI, 8, L, batch_size=8, num_ng=2, seed=9, **kw)
+
+
+def _train_sets():
+    """A: 30 pairs; B: 200 pairs, the last 40 repeating the first 40."""
+    g = np.random.default_rng(41)
+    a = np.stack([g.integers(0, TU, 30), g.integers(0, TI, 30)], 1)
+    b = np.stack([g.integers(0, TU, 200), g.integers(0, TI, 200)], 1)
+    b[160:] = b[:40]
+    return a, b
+
+
+def _same(x, y):
+    return all(np.array_equal(p, q) for p, q in zip(x, y))
+
+
+def test_set_train_again_replaces_the_set(rl):
+    sets = _train_sets()
+    want = []
+    for s in sets:  # a handle that only ever saw this set
+        f = _tiny(rl).set_train(s)
+        want.append((f.epoch_size(), f.sample(3)))
+        f.close()
+    assert want[0][0] == (90, 12) and want[1][0] == (600, 75)
+    m = _tiny(rl)
+    for k in (0, 1, 0):
+        m.set_train(sets[k])
+        assert m.epoch_size() == want[k][0]
+        assert _same(m.sample(3), want[k][1])
+    m.close()
+
+
+def test_failed_set_train_keeps_the_previous_set(rl):
+    a, _ = _train_sets()
+    m = _tiny(rl).set_train(a)
+    size, before = m.epoch_size(), m.sample(1)
+    bad = a.copy()
+    bad[17, 1] = TI
+    with pytest.raises(ValueError, match="out of range"):
+        m.set_train(bad)
+    assert m.epoch_size() == size
+    assert _same(m.sample(1), before)
+    assert m.train_steps(0, 0, 2)["steps"] == 2
+    m.close()
+
+
+def test_empty_train_set_is_a_state_error(rl):
+    a, _ = _train_sets()
+    m = _tiny(rl).set_train(a)
+    m.set_train(np.empty((0, 2), np.int64))
+    assert m.epoch_size() == (0, 0)
+    with pytest.raises(rl.BprmfError, match="error -4.*ncf_set_train first"):  # BPRMF_E_STATE
+        m.train_steps(0, 0, 0)
+    with pytest.raises(rl.BprmfError, match="error -4.*ncf_set_train first"):
+        m.sample(0, 0, 0)
+    m.close()
+
+
+def test_rejected_configs_leave_a_usable_process(rl):
+    """The last config passes the argument checks and is refused once the handle exists: the
+    forward/backward workgroup's LDS plan (ncf.hip lds_plan) holds 4 * 16 + 2 * 16 (d + 4) +
+    16 * sum_l (nout[l] + 4) floats, at 4 layers 448 + 272 d; d = 152 gives 41,792 floats =
+    167,168 B > 160 KB = 163,840 B (d = 148: 162,816 B, accepted)."""
+    with pytest.raises(rl.BprmfError, match="error -6"):  # BPRMF_E_UNSUPPORTED
+        rl.NCF(TU, TI, 6, 1, batch_size=8)
+    with pytest.raises(rl.BprmfError, match="error -6"):
+        rl.NCF(TU, TI, 8, 5, batch_size=8)
+    with pytest.raises(ValueError, match="batch_size"):
+        rl.NCF(TU, TI, 8, 1, batch_size=8193)
+    with pytest.raises(rl.BprmfError, match="error -6.*167168 B of LDS"):
+        rl.NCF(4, 4, 152, 4, batch_size=8)
+    m = _tiny(rl, L=2).set_train(_train_sets()[0])
+    assert m.train_steps(0, 0, 2)["steps"] == 2
+    m.close()
+
+
+def test_long_predict_equals_its_slices(rl):
+    """70,000 pairs: two chunks of the forward (65,536 + 4,464) and, as for every slice, the
+    branch that brings every row to the current step first."""
+    m = _tiny(rl, L=2).set_train(_train_sets()[1])
+    m.train_steps(0, 0, 3)
+    g = np.random.default_rng(43)
+    n = 70_000
+    u, i = g.integers(0, TU, n), g.integers(0, TI, n)
+    z = m.predict_logits(u, i)
+    parts = [m.predict_logits(u[s:s + 1000], i[s:s + 1000]) for s in range(0, n, 1000)]
+    assert np.array_equal(z, np.concatenate(parts))
+    assert np.isfinite(z).all() and np.unique(z).size > 100
+    m.close()
+
+
+def test_profile_counts_launches(rl):
+    """One sampler launch per call; per step one row launch (the previous step's row Adam with
+    this step's catch-up) and one forward/backward; the call's last row Adam runs alone."""
+    m = _tiny(rl).set_train(_train_sets()[0])
+    m.profile(True)
+    m.train_steps(0, 0, 5)
+    got = {k: v["count"] for k, v in m.profile_read().items()}
+    assert got == dict(sample=1, fwd_bwd=5, adam=1, catch_up=5)
+    m.profile(False)
+    m.profile(True)
+    m.train_steps(0, 5, 1)
+    got = {k: v["count"] for k, v in m.profile_read().items()}
+    assert got == dict(sample=1, fwd_bwd=1, adam=1, catch_up=1)
+    m.close()
